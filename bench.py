@@ -25,13 +25,25 @@ reduction + one X sweep + one Y sweep over the whole grid. Inputs are the refere
 initial conditions (init_test) already resident in HBM. Prints ONE JSON line on rank 0:
 
  value      = Mcells/s per sweep = cells(all ranks) · 2 sweeps · K / time / 1e6       
+ ms_per_step = milliseconds of one timed step (time / K)
+ config.hbm_placement = the draws of BlockGrid.tune_placement (done at init_test, before any timing)
+
+A plain run does only what `value` needs: set up, warm up, time the K steps, print the line. Everything else the line
+can carry is measured only with --full (and only then costs its time):
  roofline   = dominant kernel (the fused sweep, or euler_projection in --staged mode) timed live with
               HIP events on the kernel's stream; achieved = algorithmic B/cell · cells / mean duration per
               sweep; plus stream_copy_GBps_this_device / frac_of_stream_copy: the same bytes as a plain
-              4-in/4-out copy on the same device and vectors, measured right after the timed region
- config.hbm_placement = the draws of BlockGrid.tune_placement (done at init_test, before any timing)
+              4-in/4-out copy on the same device and vectors, measured right after the timed region;
+              roofline.traffic measured by two child rocprofv3 --pmc passes (N=1, unless --no-measure-traffic)
+ self_check = global mass and energy drift over the timed steps, identical lines for the 1-D test cases
  cpu_baseline = the CPU oracle ("port": OpenMP restatement of the reference's 5-pass CPU path) timed on
               this host's cores on a bounded sample (rank 0, N=1 only)
+ weak       = N > 1, default workload: the weak-scaling workload timed after the strong one
+
+--dump-outputs DIR writes, after the timed steps, what they left to a caller of the path: the state (rho, u, v, E) over
+the real cells — a fixed, seeded sample of DUMP_SAMPLE cells per field on larger grids — and the simulated time and time
+step, as DIR/<name>.npy (one set per tile, `_tile<r>`, at N > 1). The inputs are the deterministic initial conditions, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -250,6 +262,29 @@ def lines_check(test, rho):
     return (bool(np.isfinite(rho).all() and np.array_equal(rho, np.broadcast_to(line, rho.shape))), bool(np.unique(line).size > 2))
 
 
+DUMP_SAMPLE = 1 << 20           # cells per field kept by --dump-outputs: 4 fields · 8 MiB in fp64
+DUMP_SEED = 20240601
+
+
+def dump_outputs(directory, grid, gdt, suffix=""):
+    """--dump-outputs: the state the timed steps left (rho, u, v, E over the real cells, as 2-D arrays, or a sample of
+    DUMP_SAMPLE cells drawn with a fixed seed when the tile has more: the same cells for the same tile, whatever the
+    build) and the simulated time and time step, as ``directory/<name><suffix>.npy``."""
+    import numpy as np
+    from armon_amd.solver import STATE_VARS
+    os.makedirs(directory, exist_ok=True)
+    grid.params.wait()
+    nx, ny = grid.size.real_size
+    pick = None
+    if nx * ny > DUMP_SAMPLE:
+        pick = np.divmod(np.sort(np.random.default_rng(DUMP_SEED).choice(nx * ny, DUMP_SAMPLE, replace=False)), nx)
+    for f in STATE_VARS:
+        real = grid.real_view(grid.data[f].to_host())          # one field on the host at a time
+        np.save(os.path.join(directory, f + suffix + ".npy"), np.ascontiguousarray(real if pick is None else real[pick]))
+    np.save(os.path.join(directory, "time" + suffix + ".npy"), np.array([gdt.time], dtype=np.float64))
+    np.save(os.path.join(directory, "dt" + suffix + ".npy"), np.array([gdt.current_dt], dtype=np.float64))
+
+
 def placement_rate(placement, cells):
     """ms per Mcell of the chosen draw (tiles of one grid may differ in size), None when the tile was not placed."""
     if not placement or not placement.get("chosen_ms"):
@@ -421,11 +456,12 @@ def run_workload(args, dist, world, rank, local_rank, P, N_global, scaling, live
         halo_downgraded = not getattr(grid.comm, "native", False)       # what is timed below is not the library's own exchange
 
     from armon_amd.solver import conservation_vars
-    mass0, energy0 = conservation_vars(params, grid)         # self-check of the timed work, see below
-
     dominant = ("sweep_x", "sweep_y") if not args.staged else ("euler_projection",)
-    timer = EventTimer(params.device, dominant)
-    params.kernel_callbacks.append(timer)
+    timer = None
+    if args.full:
+        mass0, energy0 = conservation_vars(params, grid)     # self-check of the timed work, see below
+        timer = EventTimer(params.device, dominant)
+        params.kernel_callbacks.append(timer)
 
     def barrier():
         params.wait()
@@ -440,15 +476,17 @@ def run_workload(args, dist, world, rank, local_rank, P, N_global, scaling, live
     barrier()
     # Dominant kernels are timed with HIP events for the first cycles_timed cycles of the timed region (the event
     # pool bounds it: a tile with two remote sides launches 3 kernels per sweep — interior + 2 boundary strips).
-    cycles_timed = min(args.steps, timer.max_pairs // 6)
+    cycles_timed = min(args.steps, timer.max_pairs // 6) if timer else 0
     t0 = time.perf_counter()
     for i in range(args.steps):
-        timer.enabled = i < cycles_timed
+        if timer:
+            timer.enabled = i < cycles_timed
         solver_cycle(params, grid, last_cycle=False)
         gdt.next_cycle()
     barrier()
     elapsed = time.perf_counter() - t0
-    timer.enabled = False
+    if timer:
+        timer.enabled = False
     from armon_amd.solver import drain_halo
     drain_halo(grid)                     # the exchange posted ahead for the cycle that will not run
 
@@ -457,24 +495,27 @@ def run_workload(args, dist, world, rank, local_rank, P, N_global, scaling, live
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and primary:
+        dump_outputs(args.dump_outputs, grid, gdt, f"_tile{rank}" if world > 1 else "")
 
-    # Self-check that the timed cycles did the work: global mass and energy against the initial state, and (for the
-    # test cases that vary along one axis only) every row / column of this rank's density identical and finite.
-    import numpy as np
-    mass1, energy1 = conservation_vars(params, grid)
-    self_check = {"mass_drift": abs(mass1 - mass0) / abs(mass0), "energy_drift": abs(energy1 - energy0) / abs(energy0)}
-    if args.test in ("Sod", "Sod_y", "Bizarrium"):
-        ident, moved = lines_check(args.test, grid.real_view(grid.data["rho"].to_host()))
-        if dist is not None:                 # every rank's tile: identical lines everywhere, the waves moved somewhere
-            import torch
-            t = torch.tensor([float(ident), -float(moved)], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            ident, moved = bool(t[0].item()), bool(-t[1].item())
-        self_check["lines_identical"], self_check["moved"] = ident, moved
+    self_check, roofline = None, None
+    if args.full:
+        # Self-check that the timed cycles did the work: global mass and energy against the initial state, and (for the
+        # test cases that vary along one axis only) every row / column of this rank's density identical and finite.
+        mass1, energy1 = conservation_vars(params, grid)
+        self_check = {"mass_drift": abs(mass1 - mass0) / abs(mass0), "energy_drift": abs(energy1 - energy0) / abs(energy0)}
+        if args.test in ("Sod", "Sod_y", "Bizarrium"):
+            ident, moved = lines_check(args.test, grid.real_view(grid.data["rho"].to_host()))
+            if dist is not None:                 # every rank's tile: identical lines everywhere, the waves moved somewhere
+                import torch
+                t = torch.tensor([float(ident), -float(moved)], dtype=torch.float64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
+                dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                ident, moved = bool(t[0].item()), bool(-t[1].item())
+            self_check["lines_identical"], self_check["moved"] = ident, moved
 
     # Practical ceiling on THIS device: the same bytes (4 arrays read + 4 written) as a plain copy, no arithmetic.
     copy_gbps = None
-    if grid.alt is not None and primary:
+    if args.full and grid.alt is not None and primary:
         from armon_amd.solver import STATE_VARS
         src, dst = [grid.data[f] for f in STATE_VARS], [grid.alt[f] for f in STATE_VARS]
         nb = src[0].nbytes & ~15
@@ -494,32 +535,33 @@ def run_workload(args, dist, world, rank, local_rank, P, N_global, scaling, live
     sweeps = 2 * args.steps
     value = cells_total * sweeps / elapsed / 1e6
 
-    durs = timer.durations_ms()
-    all_ms = [d for v in durs.values() for d in v]
-    # one "launch" of the roofline = one whole sweep of the tile (its interior + boundary-strip launches together);
-    # the staged mode times euler_projection, once per sweep as well
-    sweeps_timed = 2 * cycles_timed
-    mean_ms = sum(all_ms) / max(sweeps_timed, 1)
-    bpc = B_PER_CELL[dominant[0]] // (2 if args.f32 else 1)
-    achieved = bpc * cells_local / (mean_ms * 1e-3) / 1e9 if all_ms else 0.0
-    traffic, traffic_source = pmc_traffic(args, world, N_global) if primary else (None, None)
-    if live_traffic is not None:
-        if live_traffic[0] is not None:
-            traffic, traffic_source = live_traffic
-        else:
-            traffic_source = (traffic_source or "none") + f" (live measurement failed: {live_traffic[1]})"
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                "kernel": "+".join(dominant), "bytes_per_cell": bpc, "launches_timed": len(all_ms),
-                "sweeps_timed": sweeps_timed, "mean_launch_ms": round(mean_ms, 4),
-                "per_kernel_ms": {k: round(sum(v) / max(cycles_timed * (2 if args.staged else 1), 1), 4)
-                                  for k, v in durs.items()}}     # per sweep of that axis (staged: per call)
-    # each kernel against the peak on its own (the slower one is the dominant kernel of the contract; `frac` above is the mean sweep)
-    roofline["per_kernel_frac"] = {k: round(bpc * cells_local / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-                                   for k, ms in roofline["per_kernel_ms"].items() if ms > 0 and not args.staged}
-    if copy_gbps:
-        roofline["stream_copy_GBps_this_device"] = round(copy_gbps, 1)     # measured right after the timed region
-        roofline["frac_of_stream_copy"] = round(achieved / copy_gbps, 4)
+    if timer:
+        durs = timer.durations_ms()
+        all_ms = [d for v in durs.values() for d in v]
+        # one "launch" of the roofline = one whole sweep of the tile (its interior + boundary-strip launches together);
+        # the staged mode times euler_projection, once per sweep as well
+        sweeps_timed = 2 * cycles_timed
+        mean_ms = sum(all_ms) / max(sweeps_timed, 1)
+        bpc = B_PER_CELL[dominant[0]] // (2 if args.f32 else 1)
+        achieved = bpc * cells_local / (mean_ms * 1e-3) / 1e9 if all_ms else 0.0
+        traffic, traffic_source = pmc_traffic(args, world, N_global) if primary else (None, None)
+        if live_traffic is not None:
+            if live_traffic[0] is not None:
+                traffic, traffic_source = live_traffic
+            else:
+                traffic_source = (traffic_source or "none") + f" (live measurement failed: {live_traffic[1]})"
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                    "kernel": "+".join(dominant), "bytes_per_cell": bpc, "launches_timed": len(all_ms),
+                    "sweeps_timed": sweeps_timed, "mean_launch_ms": round(mean_ms, 4),
+                    "per_kernel_ms": {k: round(sum(v) / max(cycles_timed * (2 if args.staged else 1), 1), 4)
+                                      for k, v in durs.items()}}     # per sweep of that axis (staged: per call)
+        # each kernel against the peak on its own (the slower one is the dominant kernel of the contract; `frac` above is the mean sweep)
+        roofline["per_kernel_frac"] = {k: round(bpc * cells_local / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+                                       for k, ms in roofline["per_kernel_ms"].items() if ms > 0 and not args.staged}
+        if copy_gbps:
+            roofline["stream_copy_GBps_this_device"] = round(copy_gbps, 1)     # measured right after the timed region
+            roofline["frac_of_stream_copy"] = round(achieved / copy_gbps, 4)
     res = dict(value=value, elapsed=elapsed, roofline=roofline, self_check=self_check, placement=placement,
                halo_mode=halo_mode, halo_downgraded=halo_downgraded, halo_errors=halo_errors, tile=tuple(params.N),
                cells_local=cells_local, cells_total=cells_total, sweeps=sweeps, device=params.device.name)
@@ -528,7 +570,8 @@ def run_workload(args, dist, world, rank, local_rank, P, N_global, scaling, live
         for comm in {id(c): c for c in (grid.comm, locals().get("native_comm"), locals().get("torch_comm")) if c is not None}.values():
             if hasattr(comm, "close"):
                 comm.close()                   # the library's RCCL communicators, before the launcher's
-    params.kernel_callbacks.remove(timer)
+    if timer:
+        params.kernel_callbacks.remove(timer)
     del grid
     import gc
     gc.collect()
@@ -564,34 +607,43 @@ def run_peer_workload(args, n_dev, P, N_global, device_ids, primary=True, live_t
         gdt = group.global_dt
         gdt.reset()
         group.dt_inflight.clear()
-        mass0, energy0 = group.conservation_vars()
         root = group.root
-        timer = EventTimer(root.device, ("sweep_x", "sweep_y"))
-        root.kernel_callbacks.append(timer)
+        timer = None
+        if args.full:
+            mass0, energy0 = group.conservation_vars()
+            timer = EventTimer(root.device, ("sweep_x", "sweep_y"))
+            root.kernel_callbacks.append(timer)
         for _ in range(args.warmup):
             group.solver_cycle(last_cycle=False)
             gdt.next_cycle()
         group.wait()
-        cycles_timed = min(args.steps, timer.max_pairs // 2)
+        cycles_timed = min(args.steps, timer.max_pairs // 2) if timer else 0
         t0 = time.perf_counter()
         for i in range(args.steps):
-            timer.enabled = i < cycles_timed
+            if timer:
+                timer.enabled = i < cycles_timed
             group.solver_cycle(last_cycle=False)
             gdt.next_cycle()
         group.wait()
         elapsed = time.perf_counter() - t0
-        timer.enabled = False
+        if timer:
+            timer.enabled = False
         group.drain()
         group.wait()
-        mass1, energy1 = group.conservation_vars()
-        self_check = {"mass_drift": abs(mass1 - mass0) / abs(mass0), "energy_drift": abs(energy1 - energy0) / abs(energy0)}
-        if args.test in ("Sod", "Sod_y", "Bizarrium"):
-            checks = [lines_check(args.test, g.real_view(g.data["rho"].to_host())) for g in group.grids]
-            self_check["lines_identical"] = all(c[0] for c in checks)
-            self_check["moved"] = any(c[1] for c in checks)
+        if args.dump_outputs and primary:
+            for r, g in enumerate(group.grids):
+                dump_outputs(args.dump_outputs, g, gdt, f"_tile{r}")
+        self_check, roofline = None, None
+        if args.full:
+            mass1, energy1 = group.conservation_vars()
+            self_check = {"mass_drift": abs(mass1 - mass0) / abs(mass0), "energy_drift": abs(energy1 - energy0) / abs(energy0)}
+            if args.test in ("Sod", "Sod_y", "Bizarrium"):
+                checks = [lines_check(args.test, g.real_view(g.data["rho"].to_host())) for g in group.grids]
+                self_check["lines_identical"] = all(c[0] for c in checks)
+                self_check["moved"] = any(c[1] for c in checks)
         copy_gbps = None
         g0 = group.grids[0]
-        if primary and g0.alt is not None:
+        if args.full and primary and g0.alt is not None:
             src, dst = [g0.data[f] for f in S.STATE_VARS], [g0.alt[f] for f in S.STATE_VARS]
             nb = src[0].nbytes & ~15
             copy_gbps = best_stream_copy(root.device, src, dst, nb)
@@ -599,24 +651,25 @@ def run_peer_workload(args, n_dev, P, N_global, device_ids, primary=True, live_t
         cells_local, cells_total = sizes[0], N_global[0] * N_global[1]
         sweeps = 2 * args.steps
         value = cells_total * sweeps / elapsed / 1e6
-        durs = timer.durations_ms()
-        all_ms = [d for v in durs.values() for d in v]
-        sweeps_timed = 2 * cycles_timed
-        mean_ms = sum(all_ms) / max(sweeps_timed, 1)
-        bpc = B_PER_CELL["sweep_x"] // (2 if args.f32 else 1)
-        achieved = bpc * cells_local / (mean_ms * 1e-3) / 1e9 if all_ms else 0.0
-        traffic, traffic_source = (live_traffic if live_traffic and live_traffic[0] is not None else (None, None))
-        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                    "kernel": "sweep_x+sweep_y", "bytes_per_cell": bpc, "launches_timed": len(all_ms),
-                    "sweeps_timed": sweeps_timed, "mean_launch_ms": round(mean_ms, 4),
-                    "timed_on": "tile 0: events around each whole sweep (interior + boundary strips) on its compute stream",
-                    "per_kernel_ms": {k: round(sum(v) / max(cycles_timed, 1), 4) for k, v in durs.items()}}
-        roofline["per_kernel_frac"] = {k: round(bpc * cells_local / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-                                       for k, ms in roofline["per_kernel_ms"].items() if ms > 0}
-        if copy_gbps:
-            roofline["stream_copy_GBps_this_device"] = round(copy_gbps, 1)
-            roofline["frac_of_stream_copy"] = round(achieved / copy_gbps, 4)
+        if timer:
+            durs = timer.durations_ms()
+            all_ms = [d for v in durs.values() for d in v]
+            sweeps_timed = 2 * cycles_timed
+            mean_ms = sum(all_ms) / max(sweeps_timed, 1)
+            bpc = B_PER_CELL["sweep_x"] // (2 if args.f32 else 1)
+            achieved = bpc * cells_local / (mean_ms * 1e-3) / 1e9 if all_ms else 0.0
+            traffic, traffic_source = (live_traffic if live_traffic and live_traffic[0] is not None else (None, None))
+            roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                        "kernel": "sweep_x+sweep_y", "bytes_per_cell": bpc, "launches_timed": len(all_ms),
+                        "sweeps_timed": sweeps_timed, "mean_launch_ms": round(mean_ms, 4),
+                        "timed_on": "tile 0: events around each whole sweep (interior + boundary strips) on its compute stream",
+                        "per_kernel_ms": {k: round(sum(v) / max(cycles_timed, 1), 4) for k, v in durs.items()}}
+            roofline["per_kernel_frac"] = {k: round(bpc * cells_local / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+                                           for k, ms in roofline["per_kernel_ms"].items() if ms > 0}
+            if copy_gbps:
+                roofline["stream_copy_GBps_this_device"] = round(copy_gbps, 1)
+                roofline["frac_of_stream_copy"] = round(achieved / copy_gbps, 4)
         threads = os.environ.get("ARMON_MGPU_THREADS", "1") != "0"
         mode = ("in-process tile group (armon_hip_mgpu_init, device_ids " + str(list(device_ids)) + "): one hipMemcpyPeerAsync per "
                 "face, whole cycles enqueued by armon_hip_mgpu_cycle with " + ("one host thread per tile" if threads else "the calling thread only")
@@ -747,7 +800,7 @@ def main():
     ap.add_argument("--f32", action="store_true", help="Float32 data_type (the _f32 entry points) instead of the fp64 headline")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--measure-traffic", action="store_true",
-                    help="(default at --gpus 1 when rocprofv3 is on PATH) roofline.traffic from two child rocprofv3 --pmc "
+                    help="(default with --full at --gpus 1 when rocprofv3 is on PATH) roofline.traffic from two child rocprofv3 --pmc "
                          "passes of this command (adds ≈1 min)")
     ap.add_argument("--no-measure-traffic", action="store_true",
                     help="roofline.traffic replayed from the committed passes under profiles/ instead of measured for this line")
@@ -775,6 +828,12 @@ def main():
     ap.add_argument("--config", type=int, choices=(2, 3, 4, 5), default=None,
                     help="BASELINE.json configs[N-1]: 2 = Sod 8192² Godunov, 3 = Sedov 16384², "
                          "4 = Sod 32768x16384 on 2x2, 5 = Bizarrium 32768² on 4x2")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well: roofline (per-kernel HIP events, the "
+                         "same-device copy, traffic by counters), self_check, cpu_baseline, and at N > 1 the weak workload")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state they computed (rho, u, v, E; a fixed sample on large grids), "
+                         "the simulated time and the time step as DIR/<name>.npy")
     argv = sys.argv[1:]
     args = ap.parse_args(argv)
     if args.config == 2:
@@ -815,12 +874,12 @@ def main():
     if len(P) != 2 or P[0] * P[1] != world_tiles:
         sys.exit(f"--grid {args.grid}: {world_tiles} rank(s) cannot form that process grid")
 
-    # roofline.traffic is MEASURED for the line by default (N = 1): two child passes of this command under rocprofv3 --pmc,
+    # --full: roofline.traffic is MEASURED for the line by default (N = 1): two child passes of this command under rocprofv3 --pmc,
     # before this process touches the GPU. Not from inside a profiler (tools/profile_*.sh run this file under rocprofv3:
     # a profiler in a profiled child is refused on this pool), not in the children themselves; the committed passes are
     # then replayed, and the line says which it was (roofline.traffic_source).
     live_traffic = None
-    if world_tiles == 1 and not args.no_measure_traffic and os.environ.get("ARMON_BENCH_FORCE_DIST") != "1":
+    if args.full and world_tiles == 1 and not args.no_measure_traffic and os.environ.get("ARMON_BENCH_FORCE_DIST") != "1":
         live_traffic = (None, "running under a profiler") if under_profiler() else measure_traffic(args)
 
     # a rank stuck in a collective (a peer died, a transport deadlocked) must end with a status the launcher sees
@@ -886,8 +945,8 @@ def main():
     else:
         N_primary = (args.n, args.n)                          # the same n×n grid whatever the GPU count
         scaling = "strong"
-        second = (args.n * P[0], args.n * P[1]) if world_tiles > 1 and not args.no_second else None
-    if os.environ.get("ARMON_BENCH_FORCE_SECOND") == "1" and second is None and not args.no_second:
+        second = (args.n * P[0], args.n * P[1]) if args.full and world_tiles > 1 and not args.no_second else None
+    if args.full and os.environ.get("ARMON_BENCH_FORCE_SECOND") == "1" and second is None and not args.no_second:
         second = N_primary               # (with ARMON_BENCH_FORCE_DIST=1: the second workload with ONE rank over RCCL — tearing
         #                                   the library's communicators down and building them again inside one process)
 
@@ -941,11 +1000,11 @@ def main():
                    "hbm_placement": placement, "slowest_rank": slowest_rank(placement), "device": r["device"], "halo_exchange": halo_mode,
                    "halo_exchange_downgraded": halo_downgraded,
                    "halo_exchange_error": "; ".join(halo_errors) if halo_errors else None,
-                   "launch_fallback": os.environ.get("ARMON_BENCH_FALLBACK_NOTE")},
+                   "launch_fallback": os.environ.get("ARMON_BENCH_FALLBACK_NOTE"), "full": args.full},
         "hbm_GBps_algorithmic_whole_job": round((32 if args.f32 else 64) * cells_total * sweeps / elapsed / 1e9, 1),
-        "roofline": roofline,
-        "self_check": self_check,
     }
+    if args.full:
+        out["roofline"], out["self_check"] = roofline, self_check
     # The second workload of a default N > 1 run: weak scaling (--cells² per GPU on the same process grid), timed in the same
     # processes right after the strong one and reported next to it. The line is complete at this point: a second workload
     # that raises on some rank, or hangs in a collective because it did, must not cost it — the line is printed as it stands
@@ -991,7 +1050,7 @@ def main():
             print_line()          # the other ranks may be inside a collective this one will never join: no teardown
             exit_now(3 if (args.require_native and halo_downgraded) else 4)
         watchdog.cancel()
-    if rank == 0 and world_tiles == 1 and not args.no_cpu_baseline and not args.f32:
+    if args.full and rank == 0 and world_tiles == 1 and not args.no_cpu_baseline and not args.f32:
         PHASE["name"] = "cpu baseline"
         try:
             out["cpu_baseline"] = cpu_baseline(args.test, args.scheme)

@@ -1,5 +1,6 @@
-"""bench.py's line is a contract with the driver (one JSON line on stdout: metric, value, roofline, cpu_baseline at N = 1;
-at N > 1 the STRONG workload — BASELINE's grid split over the process grid — as `value` and the weak one next to it),
+"""bench.py's line is a contract with the driver (one JSON line on stdout: metric, value, ms_per_step; with --full also
+roofline, self_check, cpu_baseline at N = 1; at N > 1 the STRONG workload — BASELINE's grid split over the process grid — as
+`value` and, with --full, the weak one next to it),
 whoever launched it: a launcher (the driver's torch.distributed.run command) or nobody (a bare `python bench.py --gpus N`
 starts its own ranks, or drives every device from one process with --transport peer). Small grids, seconds each."""
 import json
@@ -23,8 +24,44 @@ def run_line(cmd, env=None, timeout=600, rc=0):
     return json.loads(lines[0])
 
 
+def test_plain_line_carries_the_headline_only():
+    """A plain run sets up, warms up, times --steps steps and prints the line: nothing measured or checked besides."""
+    d = run_line([sys.executable, BENCH, "--cells", "1024", "--steps", "3", "--warmup", "1"])
+    assert d["metric"] == "Mcells/sec per sweep (fp64)" and d["unit"] == "Mcells/s" and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "f64" and d["config"]["full"] is False
+    assert d["value"] > 0 and abs(d["value"] - 1024 * 1024 * 2 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"]
+    assert not {"roofline", "self_check", "cpu_baseline", "weak"} & set(d), sorted(d)
+
+
+def test_dump_outputs_are_the_state_after_the_last_timed_step(tmp_path, oracle):
+    """--dump-outputs: the state after warmup + steps cycles (the oracle's, within the tuned arithmetic's tolerance), the
+    same from run to run; on a grid above the sample size a fixed sample of it, the same cells in every run."""
+    import numpy as np
+    run_line([sys.executable, BENCH, "--cells", "512", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
+    run_line([sys.executable, BENCH, "--cells", "512", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "b")])
+    assert sorted(os.listdir(tmp_path / "a")) == ["E.npy", "dt.npy", "rho.npy", "time.npy", "u.npy", "v.npy"]
+    orun, f = oracle.solve(test="Sod", N=(512, 512), maxcycle=4, maxtime=1e9)
+    for k in ("rho", "u", "v", "E"):
+        a, b = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert a.shape == (512, 512) and a.dtype == np.float64 and np.array_equal(a, b), k
+        ref = oracle.real_view(f[k], 512, 512, 4)
+        assert np.abs(a - ref).max() <= 1e-11 * np.abs(ref).max(), (k, float(np.abs(a - ref).max()))
+    time_a = np.load(tmp_path / "a" / "time.npy")
+    assert time_a.dtype == np.float64 and np.array_equal(time_a, np.load(tmp_path / "b" / "time.npy"))
+    assert abs(time_a[0] - orun.final_time) <= 1e-12 * orun.final_time, (time_a[0], orun.final_time)
+
+    run_line([sys.executable, BENCH, "--cells", "1100", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "c")])
+    run_line([sys.executable, BENCH, "--cells", "1100", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")])
+    total = 0
+    for k in ("rho", "u", "v", "E", "time", "dt"):
+        a, b = np.load(tmp_path / "c" / f"{k}.npy"), np.load(tmp_path / "d" / f"{k}.npy")
+        assert np.array_equal(a, b), k
+        total += os.path.getsize(tmp_path / "c" / f"{k}.npy")
+    assert np.load(tmp_path / "c" / "rho.npy").shape == (1 << 20,) and total <= 64 << 20
+
+
 def test_single_gpu_line_carries_the_contract():
-    d = run_line([sys.executable, BENCH, "--cells", "1024", "--steps", "3", "--warmup", "1", "--no-measure-traffic"])
+    d = run_line([sys.executable, BENCH, "--cells", "1024", "--steps", "3", "--warmup", "1", "--no-measure-traffic", "--full"])
     assert d["metric"].startswith("Mcells/sec per sweep") and d["unit"] == "Mcells/s" and d["higher_is_better"] is True
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["scaling"] == "strong" and d["vs_baseline"] is None
     assert d["dtype"] == "f64" and d["data"] == "synthetic" and "Sod 1024x1024" in d["config"]["workload"]
@@ -45,7 +82,7 @@ def test_traffic_is_measured_for_the_line_by_default():
     import shutil
     if shutil.which("rocprofv3") is None:
         pytest.skip("rocprofv3 not on PATH")
-    d = run_line([sys.executable, BENCH, "--cells", "2048", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    d = run_line([sys.executable, BENCH, "--cells", "2048", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     ro = d["roofline"]
     src = ro["traffic_source"] or ""
     if "live measurement failed" in src and ("rocprofv3 not found" in src or "ounters" in src and "unavailable" in src):
@@ -71,7 +108,7 @@ def check_two_tile_line(d):
 
 
 REHEARSAL = {"ARMON_BENCH_REHEARSAL": "1"}            # every rank / tile on this one GPU (gloo between ranks)
-SMALL = ["--gpus", "2", "--cells", "512", "--steps", "3", "--warmup", "1"]
+SMALL = ["--gpus", "2", "--cells", "512", "--steps", "3", "--warmup", "1", "--full"]
 
 
 def test_two_ranks_under_a_launcher_report_the_strong_and_the_weak_workload():
@@ -136,7 +173,7 @@ def test_one_rank_over_real_rccl_runs_both_workloads_through_the_native_cycle():
     library's own RCCL group (two communicators, the all-reduce of the next CFL step on the transfer stream), whole cycles
     through armon_hip_mgpu_cycle, the transports' self-check — and the SECOND workload in the same process, which tears the
     library's communicators down and builds them again (ARMON_BENCH_FORCE_DIST / ARMON_BENCH_FORCE_SECOND)."""
-    d = run_line([sys.executable, BENCH, "--cells", "1024", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+    d = run_line([sys.executable, BENCH, "--cells", "1024", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                  env={"ARMON_BENCH_FORCE_DIST": "1", "ARMON_BENCH_FORCE_SECOND": "1"})
     assert d["n_gpus"] == 1 and d["config"]["halo_exchange_downgraded"] is False, d["config"]["halo_exchange_error"]
     assert d["config"]["halo_exchange"].startswith("native (armon_hip_halo_exchange over RCCL")

@@ -368,6 +368,37 @@ def test_bench_launcher_helpers_kill_by_process_group_and_find_the_line(tmp_path
     assert bench.slowest_rank(pl) == 2 and bench.slowest_rank([{"rank": 0, "tries": 0}]) is None and bench.slowest_rank(None) is None
 
 
+@pytest.mark.parametrize("nx,ny,dtype", [(40, 24, np.float64), (1100, 1000, np.float32)])
+def test_bench_dump_outputs_keeps_the_real_cells_or_a_fixed_sample(tmp_path, nx, ny, dtype):
+    """bench.py --dump-outputs without any GPU (host arrays stand in for the device vectors): the real cells of rho, u, v, E
+    in the run's precision, or above DUMP_SAMPLE cells the same seeded sample in every call, plus time and dt; within 64 MB."""
+    import importlib.util
+    import types
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = 4
+    host = {f: np.random.default_rng(k).random((ny + 2 * g) * (nx + 2 * g)).astype(dtype) for k, f in enumerate(("rho", "u", "v", "E"))}
+    grid = types.SimpleNamespace(params=types.SimpleNamespace(wait=lambda: None), size=types.SimpleNamespace(real_size=(nx, ny)),
+                                 data={f: types.SimpleNamespace(to_host=lambda a=a: a.copy()) for f, a in host.items()},
+                                 real_view=lambda a: a.reshape(ny + 2 * g, nx + 2 * g)[g:g + ny, g:g + nx])
+    gdt = types.SimpleNamespace(time=dtype(0.125), current_dt=dtype(1e-3))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), grid, gdt)
+    total = 0
+    for f, a in host.items():
+        out = np.load(tmp_path / "a" / f"{f}.npy")
+        assert out.dtype == dtype and np.array_equal(out, np.load(tmp_path / "b" / f"{f}.npy"))
+        real = grid.real_view(a)
+        if nx * ny <= bench.DUMP_SAMPLE:
+            assert np.array_equal(out, real)
+        else:
+            assert out.shape == (bench.DUMP_SAMPLE,) and np.isin(out, real).all()
+        total += os.path.getsize(tmp_path / "a" / f"{f}.npy")
+    assert np.load(tmp_path / "a" / "time.npy").tolist() == [0.125] and np.load(tmp_path / "a" / "dt.npy").dtype == np.float64
+    assert total <= 64 << 20
+
+
 def test_cycle_plan_follows_split_axes(monkeypatch):
     """multi_tile.cycle_plan = the armon_cycle_plan of one solver cycle: the sweeps of split_axes (ref src/axis_splitting.jl:
     24-46) with their steps current_dt x factor, the last cycle's emit_p, cst_dt's missing reduction, the NEXT cycle's first

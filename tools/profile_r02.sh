@@ -5,11 +5,11 @@
 root=${GRAFT_REPO_ROOT:-$PWD}
 out=$root/gpurun_out/prof_r02
 mkdir -p $out
-python3 $root/bench.py > $out/r02_fused_fast_sod16384_bench.json 2> $out/bench_plain.err
+python3 $root/bench.py --full > $out/r02_fused_fast_sod16384_bench.json 2> $out/bench_plain.err
 cd /tmp && export TMPDIR=/tmp
 run() {
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python3 $root/bench.py "$@" > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python3 $root/bench.py --full "$@" > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}.err
   cp "$(find $out/$tag -name '*kernel_stats.csv' | head -1)" $out/${tag}_kernel_stats.csv
   python3 $root/tools/trace_timed_region.py "$(find $out/$tag -name '*kernel_trace.csv' | head -1)" $out/${tag}_timed_region.json 20 k_sweep k_euler_projection k_acoustic_GAD k_advection_second > /dev/null
   rm -rf $out/$tag

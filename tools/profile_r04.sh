@@ -6,12 +6,12 @@
 root=${GRAFT_REPO_ROOT:-$PWD}
 out=$root/gpurun_out/prof_r04
 mkdir -p $out
-python3 $root/bench.py > $out/r04_fused_fast_sod16384_bench.json 2> $out/bench_plain.err
+python3 $root/bench.py --full > $out/r04_fused_fast_sod16384_bench.json 2> $out/bench_plain.err
 echo "plain bench done"
 cd /tmp && export TMPDIR=/tmp
 run() {
   tag=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python3 $root/bench.py --no-measure-traffic --no-cpu-baseline "$@" > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python3 $root/bench.py --full --no-measure-traffic --no-cpu-baseline "$@" > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}.err
   cp "$(find $out/$tag -name '*kernel_stats.csv' | head -1)" $out/${tag}_kernel_stats.csv
   python3 $root/tools/trace_timed_region.py "$(find $out/$tag -name '*kernel_trace.csv' | head -1)" $out/${tag}_timed_region.json 20 k_sweep k_euler_projection k_acoustic_GAD k_advection_second k_dtCFL k_cell_update k_perfect_gas > /dev/null
   rm -rf $out/$tag

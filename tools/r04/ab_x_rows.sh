@@ -7,7 +7,7 @@ for shape in 16384x16384 8192x8192 4096x8192; do
 done
 for rows in 1 2; do
   echo "== traffic with ARMON_X_ROWS=$rows"
-  ARMON_X_ROWS=$rows python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline | python3 -c "
+  ARMON_X_ROWS=$rows python3 bench.py --full --steps 5 --warmup 1 --no-cpu-baseline | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['value'], r['per_kernel_ms'], 'traffic', r['traffic'], r['traffic']/(64*16384*16384) if r['traffic'] else None, r['traffic_source'][:40])"
 done

@@ -7,10 +7,10 @@
 export ARMON_BENCH_REHEARSAL=1
 out=gpurun_out
 for n in 2 4 6; do
-  python3 bench.py --gpus $n --cells 2048 --steps 5 --warmup 2 > $out/r05_bench_${n}rank_rehearsal.json 2> $out/r05_bench_${n}rank_rehearsal.err
+  python3 bench.py --full --gpus $n --cells 2048 --steps 5 --warmup 2 > $out/r05_bench_${n}rank_rehearsal.json 2> $out/r05_bench_${n}rank_rehearsal.err
   echo "ranks $n: rc $?"
 done
-python3 bench.py --gpus 8 --cells 4096 --steps 5 --warmup 2 --transport peer > $out/r05_bench_8tile_peer_rehearsal.json 2> $out/r05_bench_8tile_peer_rehearsal.err
+python3 bench.py --full --gpus 8 --cells 4096 --steps 5 --warmup 2 --transport peer > $out/r05_bench_8tile_peer_rehearsal.json 2> $out/r05_bench_8tile_peer_rehearsal.err
 echo "peer 8: rc $?"
 for f in $out/r05_bench_*rehearsal.json; do python3 -c "
 import json,sys

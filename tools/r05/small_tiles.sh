@@ -12,10 +12,10 @@ mkdir -p $out
 SQ="SQ_WAVE_CYCLES,SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU,SQ_INSTS_VALU SQ_WAIT_INST_ANY,SQ_ACTIVE_INST_ANY SQ_INST_CYCLES_VMEM,SQ_INSTS_VMEM_RD SQ_WAVES,SQ_WAIT_ANY,GRBM_GUI_ACTIVE"
 for shape in 4096x8192 8192x8192; do
   tag=r05_tile_${shape}${sfx}
-  python3 $root/bench.py --global $shape --grid 1x1 --steps 100 --warmup 5 --no-cpu-baseline > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+  python3 $root/bench.py --full --global $shape --grid 1x1 --steps 100 --warmup 5 --no-cpu-baseline > $out/${tag}_bench.json 2> $out/${tag}_bench.err
   echo "$tag plain done"
   ( cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python3 $root/bench.py --global $shape --grid 1x1 --steps 100 --warmup 5 --no-measure-traffic --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}.err )
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/$tag -- python3 $root/bench.py --full --global $shape --grid 1x1 --steps 100 --warmup 5 --no-measure-traffic --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}.err )
   cp "$(find $out/$tag -name '*kernel_stats.csv' | head -1)" $out/${tag}_kernel_stats.csv
   python3 $root/tools/trace_timed_region.py "$(find $out/$tag -name '*kernel_trace.csv' | head -1)" $out/${tag}_timed_region.json 100 k_sweep > /dev/null
   rm -rf $out/$tag
