@@ -68,14 +68,56 @@ def read_data_from_file(params, host, file, vars=SAVED_VARS, global_ghosts=False
         np.asarray(host[v]).reshape(-1, sx)[y0:y1, x0:x1] = vals[:, :, k]
 
 
-def write_sub_domain_file(params, grid, file_name, no_msg=False, vars=SAVED_VARS):
-    path = build_file_path(params, file_name)
-    host = grid.device_to_host(vars)
-    with open(path, "w") as f:
-        write_blocks_to_file(params, host, f, vars=vars, global_ghosts=params.write_ghosts)
+def write_sub_domain_file(params, grid, file_name, no_msg=False, vars=SAVED_VARS, coarse=False):
+    """``coarse=True`` (what ``armon`` and the animation frames pass when ``output_coarsen`` is set): the file holds the
+    state coarsened on the device, see ``write_coarse_file``; no full field goes to the host."""
+    if coarse:
+        path = write_coarse_file(params, grid.coarsen(params.output_coarsen), file_name)
+    else:
+        path = build_file_path(params, file_name)
+        host = grid.device_to_host(vars)
+        with open(path, "w") as f:
+            write_blocks_to_file(params, host, f, vars=vars, global_ghosts=params.write_ghosts)
     if not no_msg and params.is_root and params.silent < 2:
         print(f"\nWrote to files {path}_*x*")
     return path
+
+
+def write_coarse_planes_to_file(params, planes, file, vars=SAVED_VARS):
+    """``planes`` = dict name → ``(cny, cnx)`` array (``BlockGrid.coarsen``): one line per coarse cell in the cell format of
+    ``write_blocks_to_file`` (``x, y, ρ, u, v, p``, ``output_precision``), a blank line between coarse rows."""
+    fmt = ", ".join([_fmt(params.output_precision)] * len(vars)) + "\n"
+    cols = [np.asarray(planes[v]) for v in vars]
+    for j in range(cols[0].shape[0]):
+        if j != 0:
+            file.write("\n")
+        file.write("".join(fmt % vals for vals in zip(*[c[j] for c in cols])))
+
+
+def write_coarse_file(params, planes, file_name, vars=SAVED_VARS):
+    path = build_file_path(params, file_name)
+    with open(path, "w") as f:
+        write_coarse_planes_to_file(params, planes, f, vars=vars)
+    return path
+
+
+def read_coarse_file(params, file_name, vars=SAVED_VARS):
+    """Reads a file of ``write_coarse_file`` back → dict name → ``(cny, cnx)`` float64 array. The shape comes from the file
+    itself: blank lines separate the coarse rows."""
+    rows, row = [], []
+    with open(build_file_path(params, file_name)) as f:
+        for line in f:
+            if line.strip():
+                row.append([float(t) for t in line.split(",")])
+            elif row:
+                rows.append(row)
+                row = []
+    if row:
+        rows.append(row)
+    if not rows or any(len(r) != len(rows[0]) for r in rows) or any(len(c) != len(vars) for r in rows for c in r):
+        raise ValueError(f"{file_name}: not a coarse file of {len(vars)} values per line in rows of equal length")
+    vals = np.array(rows, dtype=np.float64)
+    return {v: vals[:, :, k] for k, v in enumerate(vars)}
 
 
 def write_slices_files(params, grid, file_name, vars=SAVED_VARS):
@@ -84,22 +126,22 @@ def write_slices_files(params, grid, file_name, vars=SAVED_VARS):
     ghost cells too". The reference calls ``write_slices_files`` but does not define it anywhere in src/, so the file
     names are this backend's: ``<file>_X`` (the row j = Ny÷2), ``<file>_Y`` (the column i = Nx÷2), ``<file>_diag`` (cells
     (k, k), k < min(Nx, Ny)), each in the cell format of ``write_blocks_to_file``. Single block only (a tile writes the
-    slices of its own sub-domain, with the sub-domain suffix of ``build_file_path``)."""
+    slices of its own sub-domain, with the sub-domain suffix of ``build_file_path``). The cells are picked on the device
+    (``BlockGrid.gather``: stride 1 along the row, the row pitch along the column, pitch + 1 along the diagonal): three
+    lines of cells cross PCIe, not six fields."""
     fmt = ", ".join([_fmt(params.output_precision)] * len(vars)) + "\n"
     sx = params.N[0] + 2 * params.nghost
     g = params.nghost
     (x0, x1), (y0, y1) = _rows(params, params.write_ghosts)
-    host = grid.device_to_host(vars)
-    cols = [np.asarray(host[v]).reshape(-1, sx) for v in vars]
     jm, im = g + params.N[1] // 2, g + params.N[0] // 2
     n_diag = min(x1 - x0, y1 - y0)
-    picks = {"X": [(jm, i) for i in range(x0, x1)], "Y": [(j, im) for j in range(y0, y1)],
-             "diag": [(y0 + k, x0 + k) for k in range(n_diag)]}
+    picks = {"X": (jm * sx + x0, 1, x1 - x0), "Y": (y0 * sx + im, sx, y1 - y0), "diag": (y0 * sx + x0, sx + 1, n_diag)}
     paths = []
-    for tag, cells in picks.items():
+    for tag, (start, stride, count) in picks.items():
+        cells = grid.gather(vars, start, stride, count)
         path = build_file_path(params, f"{file_name}_{tag}")
         with open(path, "w") as f:
-            f.write("".join(fmt % tuple(c[j, i] for c in cols) for j, i in cells))
+            f.write("".join(fmt % vals for vals in zip(*[cells[v] for v in vars])))
         paths.append(path)
     if params.is_root and params.silent < 2:
         print(f"\nWrote slices to {', '.join(paths)}")
@@ -125,7 +167,8 @@ def write_animation_frame(params, grid):
     if params.animation_step == 0 or (cycle - 1) % params.animation_step != 0:
         return None
     frame = (cycle - 1) // params.animation_step
-    return write_sub_domain_file(params, grid, os.path.join("anim", params.output_file) + f"_{frame:03d}", no_msg=True)
+    return write_sub_domain_file(params, grid, os.path.join("anim", params.output_file) + f"_{frame:03d}", no_msg=True,
+                                 coarse=params.output_coarsen is not None)
 
 
 def read_sub_domain_file(params, file_name, vars=SAVED_VARS):

@@ -368,6 +368,30 @@ class TileGroup:
                 out[k][oy:oy + ny, ox:ox + nx] = g.real_view(g.data[k].to_host())
         return out
 
+    def coarsen(self, factor=None, with_p=True):
+        """``BlockGrid.coarsen`` for the whole group: each tile coarsens its own cells on its device, the coarse planes are
+        assembled into the GLOBAL coarse grid on the host. Coarse cells are defined on the global grid, so every tile must
+        start on a coarse-cell boundary ((N_origin - 1) % f == 0 along both axes: a configuration error otherwise); the
+        summation order of a coarse cell does not depend on where its cells are stored, so with exact arithmetic the planes
+        equal those of the same run in a single block, bit for bit. ``factor`` defaults to the ``output_coarsen`` option."""
+        from .parameters import check_coarsen_alignment, coarse_shape, normalize_coarsen_factor
+        factor = self.root.output_coarsen if factor is None else normalize_coarsen_factor(factor)
+        if factor is None:
+            _lib.solver_error("config", "coarsen needs a factor >= 1 (or the output_coarsen option)")
+        for p in self.params:
+            check_coarsen_alignment(p, factor)
+        self.wait()
+        cnx, cny = coarse_shape(self.root.global_grid, factor)
+        out = {}
+        for p, g in zip(self.params, self.grids):
+            planes = g.coarsen(factor, with_p=with_p)
+            ox, oy = (p.N_origin[0] - 1) // factor[0], (p.N_origin[1] - 1) // factor[1]
+            for k, a in planes.items():
+                if k not in out:
+                    out[k] = np.empty((cny, cnx), dtype=a.dtype)
+                out[k][oy:oy + a.shape[0], ox:ox + a.shape[1]] = a
+        return out
+
 
 class NativeRcclExchanger:
     """One process per GPU: this rank's tile exchanges its halos and reduces dt through the library's RCCL group

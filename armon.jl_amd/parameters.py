@@ -234,7 +234,8 @@ class ArmonParameters:
     # ref src/parameters.jl:766-778 — backend specific options (like ext/ArmonKokkos.jl:83-87)
     def _init_backend(self, device_id=None, use_fused_sweep=True, exact_arithmetic=False, stream=None,
                       placement_tries=24, stream_ordered_halo=True, ctx=None, native_halo=True, overlap_halo=True, edge_stream=True,
-                      placement_min_bytes=256 << 20, placement_rounds=8, graph_cycles=False, native_cycle=True, **options):
+                      placement_min_bytes=256 << 20, placement_rounds=8, graph_cycles=False, native_cycle=True,
+                      output_coarsen=0, **options):
         """``device_id``: GPU ordinal (default LOCAL_RANK or 0). ``use_fused_sweep``: run each sweep as
         the fused HIP kernel instead of the 5 staged kernels. ``exact_arithmetic=True``: IEEE division/sqrt
         and no FMA contraction in the fused sweep — bit-identical to the staged path and to the CPU oracle, every bit,
@@ -243,8 +244,15 @@ class ArmonParameters:
         the default tuned arithmetic (shared 1-ulp reciprocals, FMAs) stays within the reference's own
         golden-file tolerance (atol 1e-13, rtol 4 eps on the Sod family). ``placement_tries``: how many
         placements of the state vectors in HBM ``init_test`` may try (0/1 = take the first; see
-        ``BlockGrid.tune_placement``)."""
+        ``BlockGrid.tune_placement``). ``output_coarsen=0 | f | (fx, fy)``: in-situ reduced output — ``write_output`` and
+        the animation frames write the state block-averaged on the device by these factors (``BlockGrid.coarsen``,
+        ``io.write_coarse_file``) instead of every cell; 0 = the full grid, as the reference does."""
         import os
+        self.output_coarsen = normalize_coarsen_factor(output_coarsen)
+        if self.output_coarsen is not None:
+            if self.write_ghosts:
+                solver_error("config", "output_coarsen averages real cells only: it cannot be combined with write_ghosts")
+            check_coarsen_alignment(self, self.output_coarsen)
         if device_id is None:
             device_id = int(os.environ.get("LOCAL_RANK", "0")) if self.use_MPI else 0
         self.device_id = int(device_id)
@@ -353,6 +361,45 @@ def cart_neighbours(coords, dims, periodic=(False, False)):
         Side.Bottom: cart_rank((cx, cy - 1), dims, periodic),
         Side.Top: cart_rank((cx, cy + 1), dims, periodic),
     }
+
+
+def normalize_coarsen_factor(factor):
+    """``0 | f | (fx, fy)`` -> ``None`` (no coarsening) or a pair of integers >= 1; anything else is a configuration error."""
+    import numbers
+
+    def integer(f):
+        if isinstance(f, bool) or not isinstance(f, (numbers.Integral, np.integer)):
+            solver_error("config", f"coarsening factors must be integers, got {f!r}")
+        return int(f)
+
+    if isinstance(factor, (tuple, list)):
+        if len(factor) != 2:
+            solver_error("config", f"a coarsening factor is an integer or a pair (fx, fy), got {factor!r}")
+        fx, fy = integer(factor[0]), integer(factor[1])
+        if fx < 1 or fy < 1:
+            solver_error("config", f"coarsening factors must be >= 1 along both axes, got {factor!r}")
+        return fx, fy
+    f = integer(factor)
+    if f < 0:
+        solver_error("config", f"coarsening factors must be >= 1 (or 0 for none), got {f}")
+    return None if f == 0 else (f, f)
+
+
+def coarse_shape(N, factor):
+    """``(cnx, cny) = (ceil(nx / fx), ceil(ny / fy))``: the coarse grid of an nx x ny block (the last coarse row / column
+    is partial when the factor does not divide the grid)."""
+    fx, fy = factor
+    return (-(-int(N[0]) // fx), -(-int(N[1]) // fy))
+
+
+def check_coarsen_alignment(params, factor):
+    """Coarse cells are defined on the GLOBAL grid: a tile can only coarsen its own cells when its first real cell starts a
+    coarse cell along both axes, (N_origin - 1) % f == 0."""
+    for d, name in enumerate("xy"):
+        if (params.N_origin[d] - 1) % factor[d] != 0:
+            solver_error("config", f"coarsening factor {factor[d]} along {name} does not respect the tile boundaries: tile "
+                                   f"{params.cart_coords} of {params.proc_dims} starts at global cell {params.N_origin[d] - 1}, "
+                                   "which is not a multiple of the factor (coarse cells may not straddle tiles)")
 
 
 def memory_required(N, nghost=4, data_type=np.float64, fused=True, transient=False):

@@ -162,6 +162,7 @@ class BlockGrid:
         self.dt_inflight = {}                  # cycle that posted it -> event slot (see post_dt_readback)
         self.comm = None                       # set by halo_exchange.setup when use_MPI
         self.halo_prefetch = None              # (axis, handle) of an exchange posted ahead of its sweep
+        self._coarse_xy = {}                   # (fx, fy) -> coordinates of the coarse cells (coarse_coordinates)
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -298,9 +299,75 @@ class BlockGrid:
         self.params.wait()
         return {f: self.data[f].to_host() for f in names}
 
+    def gather(self, names, start, stride, count):
+        """``count`` elements of each vector of ``names`` (at most 8), from flat index ``start`` on, ``stride`` apart, picked
+        on the device (armon_hip_gather_strided) → dict name → numpy array of ``count``. Only those elements cross PCIe.
+        Any of the 16 ``BlockData`` names is accepted; on the fused path one that does not exist yet is created on this
+        access, like everywhere else (``_Fields``)."""
+        params, dev = self.params, self.params.device
+        names = tuple(names)
+        out = dev.empty(max(len(names) * count, 1), params.data_type)
+        try:
+            vars_ = (C.c_void_p * len(names))(*[self.ptr(f) for f in names])
+            check(params.fn("gather_strided")(dev.ctx, self.size.n_cells, len(names), vars_, int(start), int(stride),
+                                              int(count), C.c_void_p(out.ptr)))
+            host = out.to_host()[:len(names) * count].reshape(len(names), count)
+        finally:
+            out.free()
+        return {f: host[k] for k, f in enumerate(names)}
+
+    def coarse_coordinates(self, factor):
+        """``(x, y)`` of ``coarsen``: the STORED coordinates of the first cell each coarse cell covers, taken from the block's
+        ``x`` and ``y`` vectors with the gather kernel (one row of ``x``, one column of ``y``), as ``(cny, cnx)`` arrays. They
+        do not change during a run: fetched once per factor and kept (read-only)."""
+        from .parameters import coarse_shape
+        if factor not in self._coarse_xy:
+            fx, fy = factor
+            nx, ny = self.size.real_size
+            g, pitch = self.size.ghosts, self.size.size[0]
+            cnx, cny = coarse_shape((nx, ny), factor)
+            first = g * pitch + g
+            xs = self.gather(("x",), first, min(fx, nx), cnx)["x"]
+            ys = self.gather(("y",), first, min(fy, ny) * pitch, cny)["y"]
+            x, y = np.broadcast_to(xs[None, :], (cny, cnx)).copy(), np.broadcast_to(ys[:, None], (cny, cnx)).copy()
+            x.flags.writeable = y.flags.writeable = False
+            self._coarse_xy[factor] = (x, y)
+        return self._coarse_xy[factor]
+
+    def coarsen(self, factor, with_p=True):
+        """In-situ reduced output: the state block-averaged on the device by ``factor = f | (fx, fy)``
+        (armon_hip_coarsen: ρ and p volume-averaged, u, v, E mass-weighted, real cells only) → dict of ``(cny, cnx)`` numpy
+        arrays ``rho, u, v, E`` (+ ``p`` when ``with_p``) and ``x, y``. ``x, y`` are the STORED coordinates of the first cell
+        each coarse cell covers, taken with the gather kernel, not recomputed on the host (``coarse_coordinates``). Only the
+        coarse planes cross PCIe. On the fused path ``p`` is what the last sweep that was asked for it left
+        (``solver_cycle(last_cycle=True)``). A factor other than (power of two <= 64, <= 64) goes through device scratch
+        that stays with the context: see armon_hip_coarsen in include/armon_hip.h for its size."""
+        from .parameters import coarse_shape, normalize_coarsen_factor
+        params, dev = self.params, self.params.device
+        factor = normalize_coarsen_factor(factor)
+        if factor is None:
+            solver_error("config", "coarsen needs a factor >= 1")
+        fx, fy = factor
+        nx, ny = self.size.real_size
+        cnx, cny = coarse_shape((nx, ny), factor)
+        names = STATE_VARS + (("p",) if with_p else ())
+        out = dev.empty(len(names) * cnx * cny, params.data_type)
+        try:
+            check(params.fn("coarsen")(dev.ctx, self.size.size[0], self.size.ghosts, nx, ny, fx, fy,
+                                       *[self.ptr(f) for f in STATE_VARS], self.ptr("p") if with_p else None,
+                                       C.c_void_p(out.ptr)))
+            planes = out.to_host().reshape(len(names), cny, cnx)
+        finally:
+            out.free()
+        res = {f: planes[k] for k, f in enumerate(names)}
+        res["x"], res["y"] = self.coarse_coordinates(factor)
+        return res
+
     def host_to_device(self, host):
         for f, a in host.items():
             self.data[f].copy_from_host(a)
+        if "x" in host or "y" in host:
+            self._coarse_xy.clear()
 
     def real_view(self, a):
         g = self.size.ghosts
@@ -1049,7 +1116,7 @@ def armon(params):
                 solver_error("check", f"mass or energy are not conserved: |ΔM| = {dM}, |ΔE| = {dE}")
     if params.write_output:
         from .io import write_sub_domain_file
-        write_sub_domain_file(params, grid, params.output_file)
+        write_sub_domain_file(params, grid, params.output_file, coarse=params.output_coarsen is not None)
     if params.write_slices:
         from .io import write_slices_files
         write_slices_files(params, grid, params.output_file)

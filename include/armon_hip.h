@@ -224,6 +224,32 @@ ARMON_API int armon_hip_init_test(armon_ctx*, armon_range, int test, int64_t row
         int nghost, const int64_t global_pos[2], const int64_t global_N[2],
         const double origin[2], const double dX[2], double sedov_r, const armon_block_data* data);
 
+/* ---- in-situ reduced output (no reference counterpart: the reference writes whole fields, ref src/io.jl:2-27) ---- */
+/* Conservative coarsening of one block by the integer factors (fx, fy) >= 1. The block has rows of `row_length` elements,
+ * `nghost` ghost layers and nx x ny real cells (row_length >= nx + 2 nghost); only real cells are read. Coarse cell (I, J)
+ * covers the real cells i in [I fx, min((I+1) fx, nx)), j in [J fy, min((J+1) fy, ny)) — n cells; the coarse grid is
+ * cnx x cny = ceil(nx/fx) x ceil(ny/fy). `out_dev` receives five dense planes [cny][cnx], in this order:
+ *   rho = S(rho)/n,  u = S(rho u)/S(rho),  v = S(rho v)/S(rho),  E = S(rho E)/S(rho),  p = S(p)/n
+ * (cells are uniform: volume averages of rho and p, mass-weighted averages of u, v, E; n rho_c ds summed over the coarse
+ * cells is the mass armon_hip_conservation_vars returns). `p` may be NULL: the fifth plane is then left untouched, and
+ * `out_dev` may hold four planes only. One pass over the 4 (5) vectors, no atomics; the value of a coarse cell is a fixed
+ * function of the values it covers — the same summation order (csrc/coarsen.hip) wherever the block sits in memory and
+ * whatever the grid size. fx a power of two <= 64 with fy <= 64 is one kernel and needs no scratch. Any other factor takes
+ * two kernels through the context's reduction scratch, which must hold nx * ceil(ny / min(fy, 64)) elements per plane read
+ * (4, or 5 with p): 1/64 of the fields for fy >= 64, but as much as the fields themselves for fy = 1 (8.6 GB at 16384^2
+ * fp64 without p). That scratch grows, with one stream synchronisation, the first time it is too small, stays with the
+ * context until armon_hip_destroy, and — like every reduction scratch of this library — cannot grow inside a stream
+ * capture or while a captured graph of the context is alive (ARMON_ERR_INVALID_ARG then: run the call once before
+ * capturing). Async on the context's stream. */
+ARMON_API int armon_hip_coarsen(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int64_t fx, int64_t fy,
+        const double* rho, const double* u, const double* v, const double* E, const double* p, double* out_dev);
+
+/* Strided gather: out_dev[q*count + i] = vars[q][start + i*stride], q < nvars <= 8, i < count. `vars` = HOST array of
+ * `nvars` device pointers to vectors of `n_cells` elements; a slice that leaves [0, n_cells) is refused. The middle row of a
+ * block is stride 1, its middle column stride = row pitch, its diagonal stride = row pitch + 1. Async on the stream. */
+ARMON_API int armon_hip_gather_strided(armon_ctx*, int64_t n_cells, int nvars, const double* const* vars,
+        int64_t start, int64_t stride, int64_t count, double* out_dev);
+
 /* ---- fp32 variants (ref data_type=Float32, src/parameters.jl:185): same kernels, float arrays and scalars ---- */
 typedef struct {
     float *x, *y, *rho, *u, *v, *E, *p, *c, *g, *us, *ps, *work_1, *work_2, *work_3, *work_4, *mask;
@@ -263,6 +289,10 @@ ARMON_API int armon_hip_conservation_vars_f32(armon_ctx*, armon_range, float ds,
 ARMON_API int armon_hip_init_test_f32(armon_ctx*, armon_range, int test, int64_t row_length, int64_t col_length,
         int nghost, const int64_t global_pos[2], const int64_t global_N[2],
         const float origin[2], const float dX[2], float sedov_r, const armon_block_data_f32* data);
+ARMON_API int armon_hip_coarsen_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int64_t fx, int64_t fy,
+        const float* rho, const float* u, const float* v, const float* E, const float* p, float* out_dev);
+ARMON_API int armon_hip_gather_strided_f32(armon_ctx*, int64_t n_cells, int nvars, const float* const* vars,
+        int64_t start, int64_t stride, int64_t count, float* out_dev);
 
 /* ---- fused sweep: EOS → BC (in-tile mirror) → fluxes → cell update → advection → projection ---- */
 /* One call = one directional sweep of solver_cycle (ref src/solver.jl:300-316) over one block, reading
