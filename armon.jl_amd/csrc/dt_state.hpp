@@ -1,6 +1,6 @@
 // dt_state.hpp — update_dt! + next_cycle! + the time loop's exit test on a device-resident armon_dt_state, for ONE thread
 // (ref src/solver_state.jl:102-166, src/solver.jl:350). Shared by the stand-alone step kernel (dt_state.hip) and the fold
-// of the fused dt reduction (fused_sweep_impl.hpp, armon_dt_state::auto_step).
+// of the fused dt reduction (sweep_device.hpp, armon_dt_state::auto_step).
 #pragma once
 
 #include "common.hpp"

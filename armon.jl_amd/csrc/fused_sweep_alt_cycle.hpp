@@ -1,5 +1,5 @@
 // fused_sweep_alt_cycle.hpp — armon_hip_cycle_xy, the entry point of the whole-cycle kernels of the A/B build
-// (-DARMON_ALT_KERNELS; fused_sweep_alt_kernels.hpp). Included by fused_sweep_impl.hpp at file scope, after armon_hip_sweep.
+// (-DARMON_ALT_KERNELS; fused_sweep_alt_kernels.hpp). Included by fused_sweep.hpp at file scope, after armon_hip_sweep.
 
 extern "C" int ARMON_CYCLE_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* x, const ARMON_SWEEP_DESC* y)
 {

@@ -1,7 +1,7 @@
 // fused_sweep_alt_kernels.hpp — the measured-and-rejected kernel forms of the fused sweep (profiles/NOTES.md):
 // the whole-cycle kernels k_cycle_xy / k_cycle_pc and the LDS-transposed X march k_sweep_x_lds. Correct and tested, 1.3-4x slower
 // than what the solver runs. Compiled only with -DARMON_ALT_KERNELS, into libarmon_hip_alt.so (build.py). This file is
-// included by fused_sweep_impl.hpp INSIDE its anonymous namespace, after the product kernels it shares helpers with
+// included by fused_sweep.hpp INSIDE its anonymous namespace, after the product kernels it shares helpers with
 // (sweep_args, buf_load / buf_store, cfl_track, bc_source, static_for): it is not a stand-alone header.
 
 // ---- whole cycle X then Y in ONE pass over memory (Sequential splitting) -----------------------------------------

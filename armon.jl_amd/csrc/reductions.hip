@@ -27,7 +27,7 @@ __device__ __forceinline__ T block_reduce(T v, T* lds)
 // ---- a11: dtCFL (ref src/reductions.jl:2-53) -------------------------------------------------------
 // min over the cells of min(dx / a, dy / b), a = max(|u+c|, |u-c|), b = max(|v+c|, |v-c|). A correctly rounded division
 // is monotone in its divisor, so that minimum is min(dx / max a, dy / max b) — the same bits with two divisions per
-// LAUNCH instead of two per cell (the fused sweeps reduce their CFL step the same way, fused_sweep_impl.hpp).
+// LAUNCH instead of two per cell (the fused sweeps reduce their CFL step the same way, sweep_device.hpp).
 // Two cells per lane with 16-B loads (8-B for fp32) wherever a row of the range starts on such a boundary in all three arrays
 // (every row of an even-pitched block does), one cell per lane otherwise. max(|u + c|, |u - c|) is evaluated as |u| + |c|: the
 // same bits (the two candidates are fl(|u| + |c|) and |fl(|u| - |c|)| in some order; rounding is monotone and symmetric).

@@ -270,7 +270,7 @@ __device__ __forceinline__ double sqrt_(double x)
 }
 __device__ __forceinline__ float sqrt_(float x) { return __builtin_amdgcn_sqrtf(x); }      // v_sqrt_f32: 1 ulp, no denormal scaling (operands are O(1) energies)
 
-// Two fp32 cells per lane as ONE 64-bit value (the tuned fp32 Y march, k_sweep_y2): elementwise arithmetic on this type is
+// Two fp32 cells per lane as ONE 64-bit value (the tuned fp32 Y march, k_sweep_y with two columns per lane): elementwise arithmetic on this type is
 // v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32 — one instruction for both cells — where two scalar pipelines side by side
 // left the pairing to the compiler's SLP pass (which found about half of it and paid for the rest in v_mov shuffles).
 // Same IEEE operations per component, hence the same bits as the scalar pipeline.

@@ -1,5 +1,5 @@
 // Probe (round 4): does an INTERNAL state layout with fewer streams remove the placement lottery of the fused sweeps?
-// The sweeps' access patterns without arithmetic (the X strips and the Y march of csrc/fused_sweep_impl.hpp, as in
+// The sweeps' access patterns without arithmetic (the X strips and the Y march of csrc/sweep_x_kernel.hpp / sweep_y_kernel.hpp, as in
 // probe_access.hip) copy the same 2 x 17.2 GB of a 16384² fp64 block (4 variables read, 4 written, X then Y) through:
 //   flat    8 separately allocated vectors, pitch nx + 2g                      (today: 8 streams)
 //   rows    one slab per state set, ROW-INTERLEAVED: row j of rho,u,v,E adjacent,
