@@ -243,6 +243,13 @@ extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
     const int64_t n_axis = d->axis == ARMON_AXIS_X ? d->nx : d->ny;
     ARMON_REQUIRE(!(d->bc_low || d->bc_high) || n_axis >= lag,
                   "mirror boundary needs at least %d cells along the sweep axis", lag);
+    // The in-tile mirror scales the velocities of the mirrored cell and evaluates the EOS of the ghost cell from them, where
+    // the reference copies p and c along with the state (ref src/halo_exchange.jl:2-29): the same bits when u² and v² are
+    // unchanged, i.e. for factors of magnitude 1 — the only ones the reference has (ref src/tests.jl:150-161).
+    ARMON_REQUIRE(!d->bc_low || (std::fabs(d->u_factor_low) == 1. && std::fabs(d->v_factor_low) == 1.),
+                  "mirror factors of the low side must be +1 or -1 (got %g, %g)", d->u_factor_low, d->v_factor_low);
+    ARMON_REQUIRE(!d->bc_high || (std::fabs(d->u_factor_high) == 1. && std::fabs(d->v_factor_high) == 1.),
+                  "mirror factors of the high side must be +1 or -1 (got %g, %g)", d->u_factor_high, d->v_factor_high);
     ARMON_REQUIRE(d->rho_in && d->u_in && d->v_in && d->E_in && d->rho_out && d->u_out && d->v_out && d->E_out,
                   "NULL state array");
     ARMON_REQUIRE(d->rho_in != d->rho_out && d->u_in != d->u_out && d->v_in != d->v_out && d->E_in != d->E_out,

@@ -16,6 +16,13 @@ extern "C" int ARMON_CYCLE_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* x, const A
     ARMON_REQUIRE(!x->dt_state && !y->dt_state, "the whole-cycle kernels do not read a device-resident time step (dt_state)");
     ARMON_REQUIRE(x->rho_in && x->u_in && x->v_in && x->E_in && y->rho_out && y->u_out && y->v_out && y->E_out, "NULL state array");
     ARMON_REQUIRE(x->rho_in != y->rho_out && x->u_in != y->u_out && x->v_in != y->v_out && x->E_in != y->E_out, "in and out arrays must not alias");
+    // as armon_hip_sweep, whose bits this entry point promises: the in-tile mirrors take factors of magnitude 1 only
+    for (const ARMON_SWEEP_DESC* d : {x, y}) {
+        ARMON_REQUIRE(!d->bc_low || (std::fabs(d->u_factor_low) == 1. && std::fabs(d->v_factor_low) == 1.),
+                      "mirror factors of the low %s side must be +1 or -1 (got %g, %g)", d == x ? "x" : "y", d->u_factor_low, d->v_factor_low);
+        ARMON_REQUIRE(!d->bc_high || (std::fabs(d->u_factor_high) == 1. && std::fabs(d->v_factor_high) == 1.),
+                      "mirror factors of the high %s side must be +1 or -1 (got %g, %g)", d == x ? "x" : "y", d->u_factor_high, d->v_factor_high);
+    }
     constexpr int lag = 4;
     ARMON_REQUIRE(x->nghost >= lag && x->nx >= lag && x->ny >= lag, "needs at least %d ghost layers and cells per axis", lag);
     const bool track = y->dt_cfl_out != nullptr;

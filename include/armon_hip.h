@@ -320,8 +320,15 @@ typedef struct {
     int64_t nx, ny;          /* real cells of the block                                         */
     double  dt, dx;          /* sweep time step (current_dt·factor) and cell size along axis    */
     double  gamma;           /* perfect gas only                                                */
-    double  u_factor_low, v_factor_low, u_factor_high, v_factor_high;   /* BC factors per side  */
+    /* BC factors per side (read where bc_* = 1). Each must be +1 or -1, the values the reference's test cases have (ref
+     * src/tests.jl:150-161), anything else is refused with ARMON_ERR_INVALID_ARG: the in-tile mirror evaluates the EOS of a
+     * ghost cell from the scaled velocities, where boundary_conditions! copies p and c of the mirrored cell — the same bits
+     * only while u² and v² are unchanged. (armon_hip_boundary_conditions of the staged path takes any factor.) */
+    double  u_factor_low, v_factor_low, u_factor_high, v_factor_high;
     const double *rho_in, *u_in, *v_in, *E_in;
+    /* What a sweep writes, and nothing else: of rho_out, u_out, v_out, E_out, p_out and c_out the real cells with
+     * out_lo <= i < out_hi along the sweep axis (every real cell across it) — no ghost cell, no real cell outside the piece;
+     * one element of dt_cfl_out. tests/test_gpu_sweep_random_state.py fills the arrays with a marker and checks it. */
     double *rho_out, *u_out, *v_out, *E_out;
     double *p_out;           /* nullable: EOS pressure of the PRE-sweep state (real cells)      */
     double *c_out;           /* nullable: EOS sound speed of the PRE-sweep state (real cells)   */

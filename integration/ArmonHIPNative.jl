@@ -230,6 +230,7 @@ struct SweepDesc{T}      # == armon_sweep_desc / armon_sweep_desc_f32, include/a
     axis::Cint; scheme::Cint; limiter::Cint; projection::Cint; eos::Cint; nghost::Cint
     bc_low::Cint; bc_high::Cint; exact::Cint; x_kernel::Cint
     nx::Int64; ny::Int64; dt::Float64; dx::Float64; gamma::Float64
+    # mirror factors of a side with bc_* = 1: each +1 or -1 (all Armon.boundary_condition returns); the fused sweeps refuse others
     u_factor_low::Float64; v_factor_low::Float64; u_factor_high::Float64; v_factor_high::Float64
     rho_in::Ptr{T}; u_in::Ptr{T}; v_in::Ptr{T}; E_in::Ptr{T}
     rho_out::Ptr{T}; u_out::Ptr{T}; v_out::Ptr{T}; E_out::Ptr{T}

@@ -9,6 +9,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from sweep_reference import draw_state
+
 pytestmark = pytest.mark.gpu
 
 G = 4
@@ -35,8 +37,7 @@ def rand_state(nx, ny, seed):
     rng = np.random.default_rng(seed)
     n = (nx + 2 * G) * (ny + 2 * G)
     f = {
-        "rho": rng.uniform(0.1, 2.0, n), "u": rng.uniform(-1, 1, n), "v": rng.uniform(-1, 1, n),
-        "E": rng.uniform(2.0, 4.0, n), "p": rng.uniform(0.1, 2.0, n), "c": rng.uniform(0.5, 2.0, n),
+        **draw_state(rng, n, "perfect_gas"), "p": rng.uniform(0.1, 2.0, n), "c": rng.uniform(0.5, 2.0, n),
         "g": rng.uniform(1, 2, n), "us": rng.uniform(-1, 1, n), "ps": rng.uniform(0.1, 2.0, n),
         "work_1": rng.uniform(-1, 1, n), "work_2": rng.uniform(-1, 1, n),
         "work_3": rng.uniform(-1, 1, n), "work_4": rng.uniform(-1, 1, n),
@@ -123,10 +124,7 @@ def test_bizarrium_EOS(dev, L, oracle, shape):
     rng = np.random.default_rng(2)
     n = (nx + 2 * G) * (ny + 2 * G)
     f = rand_state(nx, ny, 2)
-    f["rho"] = rng.uniform(0.9e4, 1.5e4, n)
-    f["u"] = rng.uniform(-300, 300, n)
-    f["v"] = rng.uniform(-300, 300, n)
-    f["E"] = rng.uniform(1e6, 5e6, n)
+    f.update(draw_state(rng, n, "bizarrium"))
     d = upload(dev, f)
     r = oracle.domain_range(nx, ny, G)
     oracle.lib().armon_oracle_bizarrium_EOS(r, *(oracle.ptr(f[k]) for k in ("rho", "u", "v", "E", "p", "c", "g")))

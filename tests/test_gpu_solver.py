@@ -461,6 +461,14 @@ def _whole_cycle_check(L, test, N):
     d_y = sweep_desc(params, grid, Axis.Y, dt, dy)
     d_x.exact = d_y.exact = 1
     assert L.armon_hip_cycle_xy(dev.ctx, C.byref(d_x), C.byref(d_y)) != 0
+    # ... mirror factors of another magnitude than 1 included, as by armon_hip_sweep, whose bits this entry point promises
+    for axis, field in ((0, "u_factor_low"), (1, "v_factor_high")):
+        d_x = sweep_desc(params, grid, Axis.X, dt, dx)
+        d_y = sweep_desc(params, grid, Axis.Y, dt, dy)
+        d = (d_x, d_y)[axis]
+        assert d.bc_low == 1 and d.bc_high == 1
+        setattr(d, field, -2.)
+        assert L.armon_hip_cycle_xy(dev.ctx, C.byref(d_x), C.byref(d_y)) == 1 and b"mirror factors" in L.armon_hip_last_error()
 
 
 def test_product_library_refuses_the_alternative_kernels():
