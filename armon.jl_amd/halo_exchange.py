@@ -28,10 +28,12 @@ class HaloExchanger:
     ``pack``/``unpack`` are the device kernels by default; tests may substitute host implementations
     (``host_arrays`` = dict name → numpy array) to exercise the protocol without a GPU."""
 
+    edges = None        # no edge streams: ``solver.overlapped_sweep`` finishes the exchange in order
+
     def __init__(self, params, grid=None, host_arrays=None, max_vars=7):
         import torch
         import torch.distributed as dist
-        if any(getattr(params, "periodic", (False, False))):
+        if any(params.periodic):
             # a periodic grid can make both sides of an axis talk to the SAME peer: batch_isend_irecv then depends on
             # message order, which only the library's exchange arranges (multi_gpu.hip, exchange_start)
             from ._lib import solver_error
@@ -47,7 +49,7 @@ class HaloExchanger:
         if self.device_buffers:
             params.device                      # make sure the context exists (it may adopt a torch stream)
         # RCCL + every kernel on torch's current stream: pack → send and recv → unpack are ordered on the device
-        self.stream_ordered = self.device_buffers and getattr(params, "shared_stream", False)
+        self.stream_ordered = self.device_buffers and params.shared_stream
         bs = params.block_size
         self.buf = {}
         for side in Side:

@@ -10,8 +10,9 @@ reference's ``solver_cycle`` (ref src/solver.jl:288-320) with ``block_ghost_exch
 minimum reduced on the device (ref src/solver_state.jl:89-111). The host never synchronises inside a cycle.
 
 ``NativeRcclExchanger`` is the one-process-per-GPU counterpart (``armon_hip_mgpu_init_rank``): the same native
-choreography over RCCL send/recv, plugged into ``solver.fused_sweep_overlapped`` in place of the torch.distributed
-``HaloExchanger``.
+choreography over RCCL send/recv, plugged into ``solver.overlapped_sweep`` in place of the torch.distributed
+``HaloExchanger``. Both are a ``NativeGroup`` — the wrapper of an ``armon_mgpu`` handle and of its local tiles — which is
+what ``solver.overlapped_sweep`` drives call by call and whose ``native_cycle`` enqueues a whole cycle in one call.
 """
 import ctypes as C
 import time as _time
@@ -20,11 +21,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import CyclePlan, HaloDesc, TileCycle, check
-from .blocking import Axis, Side, first_side, last_side, sides_along
+from .blocking import Axis, Side, sides_along
 from .parameters import PROC_NULL, ArmonParameters
 from . import solver as S
-
-_SIDE_TAG = {Side.Left: 0, Side.Right: 1, Side.Bottom: 2, Side.Top: 3}     # ARMON_SIDE_*
 
 
 def _halo_descs(params_list, grids, names):
@@ -70,13 +69,114 @@ def cycle_plan(params, gdt, last_cycle, prefetch=True, dt_host=None):
     return plan, len(sweeps)
 
 
-def native_cycle_usable(params):
-    """The native cycle has two forms of a sweep with remote sides: interior + edge stream (overlap), or in order."""
-    return (params.use_fused_sweep and getattr(params, "native_cycle", True)
-            and (not params.overlap_halo or params.edge_stream))
+class NativeGroup:
+    """An ``armon_mgpu`` handle and its local tiles (``params``, ``grids``): all tiles of an in-process group
+    (``TileGroup``) or this rank's one tile of an RCCL group (``NativeRcclExchanger``). It is the ``link`` of
+    ``solver.overlapped_sweep`` (start / finish / finish_edge / edge_join / edges) and the exchanger of the staged path
+    (``exchange``), and ``native_cycle`` is the one place that calls ``armon_hip_mgpu_cycle``."""
+
+    native = True
+
+    def _adopt(self, params, grids):
+        """The local tiles of ``self.handle``: check the library's topology against theirs, fetch their edge streams."""
+        L = self._L
+        self.params, self.grids, self.root = params, grids, params[0]
+        self.edges = []             # per tile: its transfer stream as a context, its two edge-dt scalars (device address)
+        for k, p in enumerate(params):
+            rank, coords, nb = C.c_int(), (C.c_int * 2)(), (C.c_int * 4)()
+            check(L.armon_hip_mgpu_tile_info(self.handle, k, C.byref(rank), C.byref(coords), C.byref(nb)))
+            # the library's topology is the reference's (and this package's) cartesian grid
+            assert rank.value == p.rank and tuple(coords) == p.cart_coords
+            assert [p.neighbours[s] for s in (Side.Left, Side.Right, Side.Bottom, Side.Top)] == list(nb)
+            self.edges.append((C.c_void_p(L.armon_hip_mgpu_edge_ctx(self.handle, k)), int(L.armon_hip_mgpu_edge_dt(self.handle, k))))
+        self.dt = grids[0].dt       # tile 0 lands the global CFL step (solver.DtReadback)
+        self._tcs = {}              # tile-cycle descriptors per ping-pong parity (key: where each tile's rho lives)
+
+    def _fn(self, name):
+        return getattr(self._L, "armon_hip_" + name + self.root.suffix)
+
+    def _tile_cycles(self):
+        key = tuple(g.data["rho"].ptr for g in self.grids)
+        if key not in self._tcs:
+            self._tcs[key] = tile_cycle_descs(self.params, self.grids)
+        return self._tcs[key]
+
+    def set_chaos(self, max_delay_us, seed=0):
+        """Test aid: random busy-wait kernels in front of the group's stream operations (armon_hip_mgpu_set_chaos)."""
+        check(self._L.armon_hip_mgpu_set_chaos(self.handle, int(max_delay_us), int(seed)))
+
+    def wait(self):
+        check(self._L.armon_hip_mgpu_sync(self.handle))       # compute and transfer streams of every local tile
+
+    def drain(self):
+        """Complete an exchange the last native cycle posted ahead and no cycle consumed → whether there was such a cycle."""
+        usable = bool(self.handle) and S.native_cycle_usable(self.root)
+        if usable:
+            check(self._fn("mgpu_drain")(self.handle, self._tile_cycles()))
+        return usable
+
+    def close(self):
+        if self.handle:
+            self._L.armon_hip_mgpu_destroy(self.handle)
+            self.handle = None
+
+    # ---- native exchange / reduction ----------------------------------------------------------------------------
+    def exchange_start(self, axis, names):
+        check(self._fn("halo_exchange_start")(self.handle, int(axis) - 1, _halo_descs(self.params, self.grids, names)))
+
+    def exchange_finish(self, axis, names):
+        check(self._fn("halo_exchange_finish")(self.handle, int(axis) - 1, _halo_descs(self.params, self.grids, names)))
+
+    def exchange_finish_edge(self, axis, names):
+        """Unpack on the transfer streams (no wait on the compute streams): the strips follow there, then ``edge_join``."""
+        check(self._fn("halo_exchange_finish_edge")(self.handle, int(axis) - 1, _halo_descs(self.params, self.grids, names)))
+
+    def start(self, sides, names):
+        """The exchanger interface (``halo_exchange.HaloExchanger``): ``sides`` are the two sides of one axis."""
+        if not any(p.neighbours[s] != PROC_NULL for p in self.params for s in sides):
+            return None
+        axis = Axis.X if sides[0] in (Side.Left, Side.Right) else Axis.Y
+        self.exchange_start(axis, names)
+        return axis, tuple(names)
+
+    def finish(self, handle):
+        if handle is not None:
+            self.exchange_finish(*handle)
+
+    def finish_edge(self, handle):
+        if handle is not None:
+            self.exchange_finish_edge(*handle)
+
+    def exchange(self, sides, names):
+        self.finish(self.start(sides, names))
+
+    def edge_join(self, with_dt):
+        ptrs = (C.c_void_p * len(self.grids))(*[g.dt_scalar.ptr for g in self.grids]) if with_dt else None
+        check(self._fn("mgpu_edge_join")(self.handle, ptrs))
+
+    def dt_allreduce(self, scalars=None):
+        """Global minimum of every local tile's device scalar (``grid.dt_scalar`` by default), in place."""
+        scalars = [g.dt_scalar for g in self.grids] if scalars is None else scalars
+        check(self._fn("dt_allreduce")(self.handle, (C.c_void_p * len(scalars))(*[a.ptr for a in scalars])))
+
+    def native_cycle(self, gdt, last_cycle):
+        """One solver cycle of every local tile in one library call (one host thread per tile inside): exchanges, sweeps,
+        the global minimum of the next CFL step and its read-back, posted on tile 0's transfer stream. What is left for the
+        host is to pick up the step the previous cycle posted."""
+        p0, dt = self.root, self.dt
+        deferred = (gdt.cycle - 1) in dt.inflight
+        plan, n_sweeps = cycle_plan(p0, gdt, last_cycle, dt_host=dt.landing())
+        check(self._fn("mgpu_cycle")(self.handle, C.byref(plan), self._tile_cycles()))
+        if n_sweeps & 1:
+            for g in self.grids:
+                g.swap_state()
+        if not p0.cst_dt:
+            dt.inflight[gdt.cycle] = self.edges[0][0]
+            if deferred:
+                gdt.update_dt(dt.take(gdt.cycle - 1))
 
 
-class TileGroup:
+class TileGroup(NativeGroup):
     """All tiles of a ``P = (px, py)`` decomposition of one problem, in this process."""
 
     def __init__(self, P, device_ids=None, force_peer_copy=False, **options):
@@ -98,41 +198,20 @@ class TileGroup:
             check(L.armon_hip_mgpu_force_peer_copy(self.handle, 1))
         for k in ("use_MPI", "device_id", "P"):
             options.pop(k, None)
-        self.params, self.grids, self._edge_ctx, self._edge_dt = [], [], [], []
+        self.params, self.grids = [], []            # (what ``close`` releases, should a tile fail to build)
         for r in range(nt):
             ctx = C.c_void_p(L.armon_hip_mgpu_ctx(self.handle, r))
-            p = ArmonParameters(**options, tile_of=(r, self.P), ctx=ctx, device_id=ids[r])
-            rank, coords, nb = C.c_int(), (C.c_int * 2)(), (C.c_int * 4)()
-            check(L.armon_hip_mgpu_tile_info(self.handle, r, C.byref(rank), C.byref(coords), C.byref(nb)))
-            # the library's topology is the reference's (and this package's) cartesian grid
-            assert rank.value == r and tuple(coords) == p.cart_coords
-            assert [p.neighbours[s] for s in (Side.Left, Side.Right, Side.Bottom, Side.Top)] == list(nb)
-            self.params.append(p)
-            self.grids.append(S.BlockGrid(p))
-            self._edge_ctx.append(C.c_void_p(L.armon_hip_mgpu_edge_ctx(self.handle, r)))
-            self._edge_dt.append(int(L.armon_hip_mgpu_edge_dt(self.handle, r)))
-        self.root = self.params[0]
+            self.params.append(ArmonParameters(**options, tile_of=(r, self.P), ctx=ctx, device_id=ids[r]))
+            self.grids.append(S.BlockGrid(self.params[r]))
+        self._adopt(self.params, self.grids)
         self.global_dt = self.grids[0].global_dt
         for g in self.grids:
             g.global_dt = self.global_dt               # one clock for every tile (ref GlobalTimeStep is global)
-        self.dt_host = None
-        self.dt_inflight = {}
-        self._tcs = {}              # tile-cycle descriptors per ping-pong parity (key: where tile 0's rho lives)
+        self.dt_inflight = self.dt.inflight
 
     def set_threads(self, on):
         """One host thread per tile inside ``armon_hip_mgpu_cycle`` (default) or everything from the calling thread."""
         check(self._L.armon_hip_mgpu_set_threads(self.handle, int(on)))
-
-    def _tile_cycles(self):
-        key = tuple(g.data["rho"].ptr for g in self.grids)
-        if key not in self._tcs:
-            self._tcs[key] = tile_cycle_descs(self.params, self.grids)
-        return self._tcs[key]
-
-    def drain(self):
-        """Complete an exchange the last native cycle posted ahead and no cycle consumed."""
-        if self.handle and native_cycle_usable(self.root):
-            check(self._fn("mgpu_drain")(self.handle, self._tile_cycles()))
 
     def close(self):
         if self.handle:
@@ -140,10 +219,8 @@ class TileGroup:
             for g in self.grids:
                 for a in list(g.data.values()) + (list(g.alt.values()) if g.alt else []) + [g.dt_scalar]:
                     a.free()
-            if self.dt_host is not None:
-                self.dt_host.free()
-            self._L.armon_hip_mgpu_destroy(self.handle)
-            self.handle = None
+                g.dt.free()
+            super().close()
             for p in self.params:
                 if p._device is not None:
                     p._device.ctx = None
@@ -153,34 +230,6 @@ class TileGroup:
             self.close()
         except Exception:
             pass
-
-    def set_chaos(self, max_delay_us, seed=0):
-        """Test aid: random busy-wait kernels in front of the group's stream operations (armon_hip_mgpu_set_chaos)."""
-        check(self._L.armon_hip_mgpu_set_chaos(self.handle, int(max_delay_us), int(seed)))
-
-    def _fn(self, name):
-        return getattr(self._L, "armon_hip_" + name + self.root.suffix)
-
-    # ---- native exchange / reduction ----------------------------------------------------------------------------
-    def exchange_start(self, axis, names):
-        check(self._fn("halo_exchange_start")(self.handle, int(axis) - 1, _halo_descs(self.params, self.grids, names)))
-
-    def exchange_finish(self, axis, names):
-        check(self._fn("halo_exchange_finish")(self.handle, int(axis) - 1, _halo_descs(self.params, self.grids, names)))
-
-    def exchange_finish_edge(self, axis, names):
-        check(self._fn("halo_exchange_finish_edge")(self.handle, int(axis) - 1, _halo_descs(self.params, self.grids, names)))
-
-    def edge_join(self, with_dt):
-        ptrs = (C.c_void_p * len(self.grids))(*[g.dt_scalar.ptr for g in self.grids]) if with_dt else None
-        check(self._fn("mgpu_edge_join")(self.handle, ptrs))
-
-    def dt_allreduce(self):
-        ptrs = (C.c_void_p * len(self.grids))(*[g.dt_scalar.ptr for g in self.grids])
-        check(self._fn("dt_allreduce")(self.handle, ptrs))
-
-    def wait(self):
-        check(self._L.armon_hip_mgpu_sync(self.handle))       # compute and transfer streams of every tile
 
     # ---- solver ---------------------------------------------------------------------------------------------------
     def init_test(self):
@@ -194,61 +243,10 @@ class TileGroup:
             mass, energy = mass + m, energy + e
         return mass, energy
 
-    def _remote(self, p, axis):
-        return (p.neighbours[first_side(axis)] != PROC_NULL, p.neighbours[last_side(axis)] != PROC_NULL)
-
-    def _fused_sweep(self, axis, dt, dx, **emit):
-        """One fused sweep of every tile: post the halos, sweep what reads no ghost cell while they travel, finish the
-        exchange, sweep the LAG-wide strips next to the remote sides."""
-        lag = S.sweep_lag(self.root)
-        i_ax = int(axis) - 1
-        any_remote = any(any(self._remote(p, axis)) for p in self.params)
-        if any_remote:
-            self.exchange_start(axis, S.STATE_VARS)
-        late = []
-        for p, g in zip(self.params, self.grids):
-            lo_r, hi_r = self._remote(p, axis)
-            n = p.N[i_ax]
-            if not (lo_r or hi_r):
-                S.fused_sweep(p, g, axis, dt, dx, swap=False, **emit)
-            elif n < 2 * lag + 1 or not p.overlap_halo:
-                late.append((p, g, None))
-            else:
-                lo, hi = (lag if lo_r else 0), (n - lag if hi_r else n)
-                S.fused_sweep(p, g, axis, dt, dx, out_range=(lo, hi), swap=False, **emit)
-                late.append((p, g, (lo, hi, n)))
-        # Edge stream (default): unpack and strips run on each tile's transfer stream, concurrent with the interiors,
-        # when every tile with a remote side overlaps (a tile too small to have an interior sweeps after the unpack, on
-        # its compute stream, so then the whole group takes the in-order form).
-        on_edge = any_remote and self.root.edge_stream and all(part is not None for _, _, part in late)
-        if any_remote:
-            (self.exchange_finish_edge if on_edge else self.exchange_finish)(axis, S.STATE_VARS)
-        sz = np.dtype(self.root.data_type).itemsize
-        for p, g, part in late:
-            if part is None:
-                S.fused_sweep(p, g, axis, dt, dx, swap=False, **emit)
-                continue
-            lo, hi, n = part
-            k = self.params.index(p)
-            for side, rng in enumerate(((0, lo), (hi, n))):
-                if rng[0] == rng[1]:
-                    continue
-                if on_edge:
-                    S.fused_sweep(p, g, axis, dt, dx, out_range=rng, swap=False, ctx=self._edge_ctx[k],
-                                  dt_out=self._edge_dt[k] + side * sz, **emit)
-                else:
-                    S.fused_sweep(p, g, axis, dt, dx, out_range=rng, swap=False, dt_accumulate=True, **emit)
-        if on_edge:
-            self.edge_join(bool(emit.get("emit_dt")))
-        for g in self.grids:
-            g.swap_state()
-
     def _staged_sweep(self, axis, dt, dx):
         for p, g in zip(self.params, self.grids):
             S.update_EOS(p, g, axis)
-        if any(any(self._remote(p, axis)) for p in self.params):
-            self.exchange_start(axis, S.COMM_VARS)
-            self.exchange_finish(axis, S.COMM_VARS)
+        self.exchange(sides_along(axis), S.COMM_VARS)
         for p, g in zip(self.params, self.grids):
             for side in sides_along(axis):
                 if p.neighbours[side] == PROC_NULL:
@@ -265,53 +263,24 @@ class TileGroup:
                                         g.ptr("c"), C.c_void_p(g.dt_scalar.ptr)))
         self.dt_allreduce()
 
-    def _post_dt_readback(self):
-        """Tile 0's scalar (already the global minimum, ordered on its stream) into a pinned slot + event."""
-        p, g, cycle = self.root, self.grids[0], self.global_dt.cycle
-        if self.dt_host is None:
-            self.dt_host = p.device.pinned(2, p.data_type)
-        self.dt_host.copy_from_device_async(g.dt_scalar, n=1, dst_offset=cycle & 1)
-        p.device.event_record(S.DT_EVENT_SLOT + (cycle & 1))
-        self.dt_inflight[cycle] = S.DT_EVENT_SLOT + (cycle & 1)
-
-    def _take_dt_readback(self, posted_in_cycle):
-        slot = self.dt_inflight.pop(posted_in_cycle)
-        if isinstance(slot, tuple):                       # posted by armon_hip_mgpu_cycle: the event lives in tile 0's edge context
-            check(self._L.armon_hip_event_sync(self._edge_ctx[0], slot[1]))
-        else:
-            self.root.device.event_sync(slot)
-        return float(self.dt_host.array[posted_in_cycle & 1])
-
     def solver_cycle(self, last_cycle=True):
         """ref src/solver.jl:288-320 over every tile."""
-        p0, gdt = self.root, self.global_dt
+        p0, gdt, readback, scalar = self.root, self.global_dt, self.dt, self.grids[0].dt_scalar
         fused = p0.use_fused_sweep
-        deferred = (gdt.cycle - 1) in self.dt_inflight
+        deferred = (gdt.cycle - 1) in readback.inflight
         if gdt.cycle == 0:
             for p, g in zip(self.params, self.grids):
                 S.update_EOS(p, g)
         if not deferred and not p0.cst_dt:
             self._local_dt_to_device()
-            self._post_dt_readback()
-            gdt.update_dt(self._take_dt_readback(gdt.cycle))
+            readback.post(gdt.cycle, scalar)     # tile 0's scalar: already the global minimum, ordered on its stream
+            gdt.update_dt(readback.take(gdt.cycle))
             if fused and gdt.cycle == 0:
                 for g in self.grids:
                     g.release_scratch()          # c, g: only the EOS + dtCFL of cycle 0 needed them
-        if native_cycle_usable(p0):
-            # the whole cycle of every tile in one library call (one host thread per tile inside)
-            if self.dt_host is None:
-                self.dt_host = p0.device.pinned(2, p0.data_type)
-            plan, n_sweeps = cycle_plan(p0, gdt, last_cycle, dt_host=self.dt_host)
-            check(self._fn("mgpu_cycle")(self.handle, C.byref(plan), self._tile_cycles()))
-            if n_sweeps & 1:
-                for g in self.grids:
-                    g.swap_state()
-            if not p0.cst_dt:
-                # the library reduced the next CFL step and posted its read-back on tile 0's transfer stream
-                self.dt_inflight[gdt.cycle] = ("edge", plan.dt_event_slot)
-                if deferred:
-                    gdt.update_dt(self._take_dt_readback(gdt.cycle - 1))
-            return
+        if S.native_cycle_usable(p0):
+            return self.native_cycle(gdt, last_cycle)
+        tiles = list(zip(self.params, self.grids))
         sweeps = S.split_axes(p0.axis_splitting, gdt.cycle)
         for k, (axis, dt_factor) in enumerate(sweeps):
             dx = p0.cell_size(int(axis) - 1)
@@ -320,12 +289,12 @@ class TileGroup:
                 self._staged_sweep(axis, dt, dx)
                 continue
             last = k == len(sweeps) - 1
-            self._fused_sweep(axis, dt, dx, emit_p=last and last_cycle, emit_dt=last and not p0.cst_dt)
+            S.overlapped_sweep(tiles, self, axis, dt, dx, emit_p=last and last_cycle, emit_dt=last and not p0.cst_dt)
             if last and not p0.cst_dt:
                 self.dt_allreduce()
-                self._post_dt_readback()
+                readback.post(gdt.cycle, scalar)
                 if deferred:
-                    gdt.update_dt(self._take_dt_readback(gdt.cycle - 1))
+                    gdt.update_dt(readback.take(gdt.cycle - 1))
 
     def time_loop(self):
         """ref src/solver.jl:323-403"""
@@ -336,12 +305,7 @@ class TileGroup:
         t1 = _time.perf_counter_ns()
         maxtime = p0.T(p0.maxtime)
         while gdt.time < maxtime and gdt.cycle < p0.maxcycle:
-            if p0.cst_dt:
-                ends = p0.T(gdt.time + gdt.current_dt) >= maxtime or gdt.cycle + 1 >= p0.maxcycle
-            else:
-                ends = (gdt.cycle + 1 >= p0.maxcycle or gdt.current_dt == 0
-                        or p0.T(gdt.time + gdt.current_dt) >= maxtime)
-            self.solver_cycle(last_cycle=ends)
+            self.solver_cycle(last_cycle=S.cycle_ends(p0, gdt))
             gdt.next_cycle()
         self.drain()
         self.wait()
@@ -393,20 +357,19 @@ class TileGroup:
         return out
 
 
-class NativeRcclExchanger:
+class NativeRcclExchanger(NativeGroup):
     """One process per GPU: this rank's tile exchanges its halos and reduces dt through the library's RCCL group
     (``armon_hip_mgpu_init_rank``). Same interface as ``halo_exchange.HaloExchanger`` (start / finish / exchange /
-    allreduce_min_device_async), so ``solver.fused_sweep_overlapped`` and the staged ``block_ghost_exchange`` drive
+    allreduce_min_device_async), so ``solver.overlapped_sweep`` and the staged ``block_ghost_exchange`` drive
     it unchanged. The rendezvous (128-byte RCCL ids from rank 0) travels through torch.distributed's store — the
     launcher's job, as MPI_Bcast would be for a Julia host."""
 
     stream_ordered = True           # everything is ordered on the device: the host never waits inside a cycle
-    native = True
 
     def __init__(self, params, grid):
         import torch.distributed as dist
         L = _lib.lib()
-        self.params, self.grid, self._L = params, grid, L
+        self._L = L
         group = params.global_comm
         buf = C.create_string_buffer(_lib.MGPU_ID_BYTES)
         obj = [None]
@@ -445,93 +408,18 @@ class NativeRcclExchanger:
             self.close()                 # the prepared handle (context, streams, scratch) does not outlive a failed connect
             raise
         # the group made its own context on that same stream; sweeps stay on params.device (same stream → same order)
-        rank, coords, nb = C.c_int(), (C.c_int * 2)(), (C.c_int * 4)()
-        check(L.armon_hip_mgpu_tile_info(self.handle, 0, C.byref(rank), C.byref(coords), C.byref(nb)))
-        assert rank.value == params.rank and tuple(coords) == params.cart_coords
-        assert [params.neighbours[s] for s in (Side.Left, Side.Right, Side.Bottom, Side.Top)] == list(nb)
-        self.edge_ctx = C.c_void_p(L.armon_hip_mgpu_edge_ctx(self.handle, 0))      # this tile's transfer stream as a context
-        self.edge_dt = int(L.armon_hip_mgpu_edge_dt(self.handle, 0))
-        self._tcs = {}
-
-    def _fn(self, name):
-        return getattr(self._L, "armon_hip_" + name + self.params.suffix)
-
-    def _desc(self, names):
-        return _halo_descs([self.params], [self.grid], names)
-
-    def start(self, sides, names):
-        sides = [s for s in sides if self.params.neighbours[s] != PROC_NULL]
-        if not sides:
-            return None
-        axis = Axis.X if sides[0] in (Side.Left, Side.Right) else Axis.Y
-        check(self._fn("halo_exchange_start")(self.handle, int(axis) - 1, self._desc(names)))
-        return axis, tuple(names)
-
-    def finish(self, handle):
-        if handle is None:
-            return
-        axis, names = handle
-        check(self._fn("halo_exchange_finish")(self.handle, int(axis) - 1, self._desc(names)))
-
-    def finish_edge(self, handle):
-        """Unpack on the transfer stream (no wait on the compute stream): the strips follow there, then ``edge_join``."""
-        if handle is None:
-            return
-        axis, names = handle
-        check(self._fn("halo_exchange_finish_edge")(self.handle, int(axis) - 1, self._desc(names)))
-
-    def edge_join(self, dt_scalar=None):
-        ptrs = (C.c_void_p * 1)(dt_scalar.ptr) if dt_scalar is not None else None
-        check(self._fn("mgpu_edge_join")(self.handle, ptrs))
-
-    def exchange(self, sides, names):
-        self.finish(self.start(sides, names))
+        self._adopt([params], [grid])
 
     def allreduce_min_device_async(self, scalar):
-        ptrs = (C.c_void_p * 1)(scalar.ptr)
-        check(self._fn("dt_allreduce")(self.handle, ptrs))
-
-    def set_chaos(self, max_delay_us, seed=0):
-        """Test aid: random busy-wait kernels in front of the group's stream operations (armon_hip_mgpu_set_chaos)."""
-        check(self._L.armon_hip_mgpu_set_chaos(self.handle, int(max_delay_us), int(seed)))
-
-    # the whole cycle of this rank's tile in one library call (solver.solver_cycle takes this branch when it can)
-    native_cycle = True
-
-    def _tile_cycles(self):
-        key = self.grid.data["rho"].ptr
-        if key not in self._tcs:
-            self._tcs[key] = tile_cycle_descs([self.params], [self.grid])
-        return self._tcs[key]
-
-    def cycle(self, gdt, last_cycle):
-        """One solver cycle (exchanges, sweeps, the global minimum of the next CFL step and its read-back, posted on the
-        transfer stream) → the event slot of that read-back in the edge context, or None (cst_dt)."""
-        grid = self.grid
-        if grid.dt_host is None:
-            grid.dt_host = self.params.device.pinned(2, self.params.data_type)
-        plan, n_sweeps = cycle_plan(self.params, gdt, last_cycle, dt_host=grid.dt_host)
-        check(self._fn("mgpu_cycle")(self.handle, C.byref(plan), self._tile_cycles()))
-        if n_sweeps & 1:
-            grid.swap_state()
-        return None if self.params.cst_dt else plan.dt_event_slot
-
-    def event_sync(self, slot):
-        check(self._L.armon_hip_event_sync(self.edge_ctx, slot))
+        self.dt_allreduce([scalar])
 
     def drain(self):
         """End of a run: complete the exchange posted ahead, and let the transfer stream finish (the last reduction and its
         read-back are still on it; ``params.wait()`` only covers the compute stream)."""
-        if self.handle and native_cycle_usable(self.params):
-            check(self._fn("mgpu_drain")(self.handle, self._tile_cycles()))
-            check(self._L.armon_hip_mgpu_sync(self.handle))
+        if super().drain():
+            self.wait()
 
     def allreduce_host(self, values, op):
         v = (C.c_double * len(values))(*values)
         check(self._L.armon_hip_mgpu_allreduce_host(self.handle, 0 if op == "sum" else 1, len(values), v))
         return list(v)
-
-    def close(self):
-        if self.handle:
-            self._L.armon_hip_mgpu_destroy(self.handle)
-            self.handle = None

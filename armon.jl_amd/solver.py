@@ -158,8 +158,8 @@ class BlockGrid:
         self.placement = None                  # report of tune_placement (bench / tests)
         self.global_dt = GlobalTimeStep(params)
         self.dt_scalar = dev.zeros(2, dt_)     # device scalar written by the fused dt reduction
-        self.dt_host = None                    # pinned landing zone of dt_scalar, one slot per cycle parity
-        self.dt_inflight = {}                  # cycle that posted it -> event slot (see post_dt_readback)
+        self.dt = DtReadback(params)           # deferred read-back of dt_scalar
+        self.dt_inflight = self.dt.inflight    # (the name the drivers clear between runs)
         self.comm = None                       # set by halo_exchange.setup when use_MPI
         self.halo_prefetch = None              # (axis, handle) of an exchange posted ahead of its sweep
         self._coarse_xy = {}                   # (fx, fy) -> coordinates of the coarse cells (coarse_coordinates)
@@ -212,10 +212,10 @@ class BlockGrid:
         ``keep_state=True``: ``armon_hip_tune_placement`` moves a LIVE state around (4 more vectors park it meanwhile). ~20 ms per try, outside any timed region.
         Returns the report also stored in ``self.placement``."""
         params, dev = self.params, self.params.device
-        tries = getattr(params, "placement_tries", 0)
+        tries = params.placement_tries
         nbytes = self.data["rho"].nbytes
         if min_bytes is None:
-            min_bytes = getattr(params, "placement_min_bytes", 256 << 20)
+            min_bytes = params.placement_min_bytes
         if spare is None:
             spare = 8
         if self.alt is None or tries <= 1 or nbytes < min_bytes:
@@ -244,7 +244,7 @@ class BlockGrid:
         # first would hand back the same memory) and the search is repeated with the best assignment so far as its
         # first draw, at most `placement_rounds` times. (Arithmetic-bound sweeps — exact flavour, Bizarrium — may never
         # reach the mark: they just use their rounds.)
-        rounds = max(1, int(getattr(params, "placement_rounds", 3))) if not keep_state else 1
+        rounds = max(1, params.placement_rounds) if not keep_state else 1
         # (fp32 sweeps top out at 0.89-0.91 of that rate, so their mark sits at 0.88: the search must be able to stop)
         fast_frac = 0.88 if np.dtype(params.data_type).itemsize == 4 else 0.93
         fast_ms = 2 * 8 * nbytes / (fast_frac * 6.29e12) * 1e3
@@ -430,10 +430,10 @@ def tune_staged_placement(params, grid, min_bytes=None):
     assignments — of 16 among the 16 vectors and 8 spares that are freed afterwards — are timed with one staged cycle (X then Y: EOS, boundary conditions, fluxes, cell update, advection,
     projection) on the initial condition, the fastest is kept. ≈40 ms per try, before any timed region."""
     import random
-    tries = getattr(params, "placement_tries", 0)
+    tries = params.placement_tries
     nbytes = grid.data["rho"].nbytes
     if min_bytes is None:
-        min_bytes = getattr(params, "placement_min_bytes", 256 << 20)
+        min_bytes = params.placement_min_bytes
     # a tile with a remote side (an MPI rank, or a tile of an in-process group: use_MPI is False there and grid.comm is
     # None) cannot run the timing cycle below on its own — its ghost exchange needs the neighbours
     if tries <= 1 or nbytes < min_bytes or params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
@@ -446,7 +446,7 @@ def tune_staged_placement(params, grid, min_bytes=None):
         vectors += [dev.empty(vectors[0].n, vectors[0].dtype) for _ in range(max(n_spare, 0))]
     except _lib.SolverException:
         pass
-    tries = min(12, getattr(params, "placement_tries", 0))
+    tries = min(12, params.placement_tries)
     rng = random.Random(0x5EED)
     dx = params.cell_size(0)
     dt = params.T(0.2) * dx
@@ -668,52 +668,73 @@ def sweep_desc(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=F
     return d
 
 
-def fused_sweep_overlapped(params, grid, axis, dt, dx, **emit):
-    """Fused sweep of a tile with process boundaries along ``axis``: the halo exchange of (ρ,u,v,E) runs while
-    the interior — the cells at least LAG away from the remote sides, which read no ghost cell — is computed;
-    the LAG-wide boundary strips follow once the ghosts are unpacked (ref src/solver.jl:58-285 gets the same
-    overlap from its async block state machine)."""
-    lag = sweep_lag(params)
-    n = params.N[int(axis) - 1]
-    lo_remote = params.neighbours[first_side(axis)] != PROC_NULL
-    hi_remote = params.neighbours[last_side(axis)] != PROC_NULL
-    comm = grid.comm
-    if not (lo_remote or hi_remote):
-        return fused_sweep(params, grid, axis, dt, dx, **emit)
-    if n < 2 * lag + 1 or not getattr(params, "overlap_halo", True):
-        comm.exchange(sides_along(axis), STATE_VARS)
-        return fused_sweep(params, grid, axis, dt, dx, **emit)
+def overlapped_sweep(tiles, link, axis, dt, dx, prefetched=None, **emit):
+    """One fused sweep of every ``(params, grid)`` of ``tiles`` — this rank's tile, or all tiles of an in-process group — with
+    the halo exchange of (ρ,u,v,E) along ``axis`` running while the interiors are computed: post the halos (or take the
+    handle ``prefetched`` at the end of the previous cycle), sweep what reads no ghost cell (the cells at least LAG away from
+    the remote sides; everything for a tile without one), finish the exchange, sweep the LAG-wide strips next to the remote
+    sides, swap (ref src/solver.jl:58-285 gets the same overlap from its async block state machine).
+    ``link`` moves the halos: ``start(sides, names)`` → handle or None, ``finish(handle)``, and for the library's groups
+    ``edges`` (per tile its transfer stream as a context and its two edge-dt scalars; None for torch's ``HaloExchanger``),
+    ``finish_edge(handle)`` and ``edge_join(with_dt)``: unpack and strips then run on each tile's transfer stream, concurrent
+    with the interiors. That form needs every tile with a remote side to overlap — a tile too small to have an interior, or
+    ``overlap_halo=False``, sweeps after the unpack on its compute stream, so then the whole group takes the in-order form."""
+    p0 = tiles[0][0]
+    lag = sweep_lag(p0)
+    i_ax = int(axis) - 1
+    handle = prefetched if prefetched is not None else link.start(sides_along(axis), STATE_VARS)
+    late = []
+    for k, (p, g) in enumerate(tiles):
+        lo_r = p.neighbours[first_side(axis)] != PROC_NULL
+        hi_r = p.neighbours[last_side(axis)] != PROC_NULL
+        n = p.N[i_ax]
+        if not (lo_r or hi_r):
+            fused_sweep(p, g, axis, dt, dx, swap=False, **emit)
+        elif n < 2 * lag + 1 or not p.overlap_halo:
+            late.append((k, p, g, None))
+        else:
+            lo, hi = (lag if lo_r else 0), (n - lag if hi_r else n)
+            fused_sweep(p, g, axis, dt, dx, out_range=(lo, hi), swap=False, **emit)
+            late.append((k, p, g, ((0, lo), (hi, n))))
+    on_edge = bool(late) and link.edges is not None and p0.edge_stream and all(strips is not None for *_, strips in late)
+    if on_edge:
+        link.finish_edge(handle)
+    else:
+        link.finish(handle)
+    sz = np.dtype(p0.data_type).itemsize
+    for k, p, g, strips in late:
+        if strips is None:
+            fused_sweep(p, g, axis, dt, dx, swap=False, **emit)
+            continue
+        for side, rng in enumerate(strips):
+            if rng[0] == rng[1]:
+                continue
+            if on_edge:
+                ctx, edge_dt = link.edges[k]
+                fused_sweep(p, g, axis, dt, dx, out_range=rng, swap=False, ctx=ctx, dt_out=edge_dt + side * sz, **emit)
+            else:
+                fused_sweep(p, g, axis, dt, dx, out_range=rng, swap=False, dt_accumulate=True, **emit)
+    if on_edge:
+        link.edge_join(bool(emit.get("emit_dt")))
+    for _, g in tiles:
+        g.swap_state()
+
+
+def rank_sweep(params, grid, axis, dt, dx, **emit):
+    """``overlapped_sweep`` of this rank's tile over ``grid.comm``, with the exchange ``prefetch_halo`` may have posted."""
+    handle = None
     if grid.halo_prefetch is not None and grid.halo_prefetch[0] == axis:
-        handle = grid.halo_prefetch[1]            # posted at the end of the previous cycle (prefetch_halo)
-        grid.halo_prefetch = None
+        handle, grid.halo_prefetch = grid.halo_prefetch[1], None
     else:
         drain_halo(grid)
-        handle = comm.start(sides_along(axis), STATE_VARS)
-    lo, hi = (lag if lo_remote else 0), (n - lag if hi_remote else n)
-    fused_sweep(params, grid, axis, dt, dx, out_range=(lo, hi), swap=False, **emit)
-    if getattr(comm, "edge_ctx", None) and getattr(params, "edge_stream", True):
-        # the library's group: unpack and strips on the tile's transfer stream, in the shadow of the interior
-        comm.finish_edge(handle)
-        sz = np.dtype(params.data_type).itemsize
-        for k, (remote, rng) in enumerate(((lo_remote, (0, lag)), (hi_remote, (n - lag, n)))):
-            if remote:
-                fused_sweep(params, grid, axis, dt, dx, out_range=rng, swap=False, ctx=comm.edge_ctx,
-                            dt_out=comm.edge_dt + k * sz, **emit)
-        comm.edge_join(grid.dt_scalar if emit.get("emit_dt") else None)
-    else:
-        comm.finish(handle)
-        if lo_remote:
-            fused_sweep(params, grid, axis, dt, dx, out_range=(0, lag), swap=False, dt_accumulate=True, **emit)
-        if hi_remote:
-            fused_sweep(params, grid, axis, dt, dx, out_range=(n - lag, n), swap=False, dt_accumulate=True, **emit)
-    grid.swap_state()
+    overlapped_sweep([(params, grid)], grid.comm, axis, dt, dx, prefetched=handle, **emit)
 
 
 def prefetch_halo(params, grid):
     """Post the halo exchange of the NEXT cycle's first sweep right after this cycle's last sweep: it depends on
     the state only, not on the next dt, so it travels while the dt reduction is folded, all-reduced and read
     back by the host, and the next cycle's interior sweep can start as soon as its dt is known."""
-    if not (params.use_MPI and params.use_fused_sweep) or grid.comm is None or not getattr(params, "overlap_halo", True):
+    if not (params.use_MPI and params.use_fused_sweep) or grid.comm is None or not params.overlap_halo:
         return
     axis = split_axes(params.axis_splitting, grid.global_dt.cycle + 1)[0][0]
     remote = [s for s in sides_along(axis) if params.neighbours[s] != PROC_NULL]
@@ -725,7 +746,7 @@ def prefetch_halo(params, grid):
 
 def drain_halo(grid):
     """Complete a prefetched exchange nobody consumed (end of a run, change of plan)."""
-    if getattr(grid.comm, "native_cycle", False):
+    if getattr(grid.comm, "native", False):
         grid.comm.drain()                        # what the library's own cycle posted ahead
     if grid.halo_prefetch is not None:
         grid.comm.finish(grid.halo_prefetch[1])
@@ -752,29 +773,57 @@ def next_time_step(params, grid):
 DT_EVENT_SLOT = 1012       # event-pool slots 1012, 1013: one per parity of the posting cycle
 
 
+class DtReadback:
+    """The deferred read-back of a CFL step: the pinned landing zone (one slot per parity of the posting cycle) and, per
+    posting cycle still in flight, the context its event (slot ``DT_EVENT_SLOT`` + parity) was recorded in — the compute
+    context of the block, or the transfer stream of tile 0 when the library's own cycle posted it."""
+
+    def __init__(self, params):
+        self.params, self.host, self.inflight = params, None, {}
+
+    def landing(self):
+        if self.host is None:
+            self.host = self.params.device.pinned(2, self.params.data_type)
+        return self.host
+
+    def post(self, cycle, scalar):
+        """After the last sweep of ``cycle`` reduced the next cycle's L into ``scalar`` (already the global minimum, or
+        all-reduced on the host by the taker): asynchronous copy into the slot + event, on the compute stream."""
+        dev = self.params.device
+        self.landing().copy_from_device_async(scalar, n=1, dst_offset=cycle & 1)
+        dev.event_record(DT_EVENT_SLOT + (cycle & 1))
+        self.inflight[cycle] = dev.ctx
+
+    def take(self, cycle):
+        """The CFL step posted by ``cycle`` (blocks only if the GPU has not got there yet)."""
+        check(self.params.device._L.armon_hip_event_sync(self.inflight.pop(cycle), DT_EVENT_SLOT + (cycle & 1)))
+        return float(self.host.array[cycle & 1])
+
+    def free(self):
+        if self.host is not None:
+            self.host.free()
+            self.host = None
+
+
 def post_dt_readback(params, grid):
     """After the last sweep of the current cycle (which reduced the next cycle's L into ``grid.dt_scalar``)."""
-    dev, cycle = params.device, grid.global_dt.cycle
-    if grid.dt_host is None:
-        grid.dt_host = dev.pinned(2, params.data_type)
-    if grid.comm is not None and getattr(grid.comm, "stream_ordered", False):
+    if getattr(grid.comm, "stream_ordered", False):
         grid.comm.allreduce_min_device_async(grid.dt_scalar)      # RCCL, in place, ordered on the stream
-    grid.dt_host.copy_from_device_async(grid.dt_scalar, n=1, dst_offset=cycle & 1)
-    dev.event_record(DT_EVENT_SLOT + (cycle & 1))
-    grid.dt_inflight[cycle] = DT_EVENT_SLOT + (cycle & 1)
+    grid.dt.post(grid.global_dt.cycle, grid.dt_scalar)
 
 
 def take_dt_readback(params, grid, posted_in_cycle):
-    """Global CFL step posted by ``posted_in_cycle`` (blocks only if the GPU has not got there yet)."""
-    slot = grid.dt_inflight.pop(posted_in_cycle)
-    if isinstance(slot, tuple):                   # posted by armon_hip_mgpu_cycle on the tile's transfer stream (its edge context)
-        grid.comm.event_sync(slot[1])
-    else:
-        params.device.event_sync(slot)
-    local_dt = float(grid.dt_host.array[posted_in_cycle & 1])
-    if grid.comm is not None and getattr(grid.comm, "stream_ordered", False):
+    """Global CFL step posted by ``posted_in_cycle``."""
+    local_dt = grid.dt.take(posted_in_cycle)
+    if getattr(grid.comm, "stream_ordered", False):
         return local_dt                                           # already the minimum over the ranks
     return global_min(params, local_dt)
+
+
+def native_cycle_usable(params):
+    """The one-call cycle of the library's groups (armon_hip_mgpu_cycle) has two forms of a sweep with remote sides:
+    interior + edge stream (overlap), or in order."""
+    return params.use_fused_sweep and params.native_cycle and (not params.overlap_halo or params.edge_stream)
 
 
 def _checkpoint(params, grid, label, axis=Axis.X):
@@ -803,17 +852,11 @@ def solver_cycle(params, grid, last_cycle=True):
             grid.release_scratch()               # c, g: only the EOS + dtCFL of cycle 0 needed them
     if _checkpoint(params, grid, "time_step"):
         return True
-    if params.use_MPI and getattr(grid.comm, "native_cycle", False) and not params.compare:
-        from .multi_tile import native_cycle_usable
-        if native_cycle_usable(params):
-            # the library's own group: exchanges, sweeps and the all-reduce of the next CFL step in ONE call
-            # (armon_hip_mgpu_cycle); what is left for the host is the read-back of that scalar, one cycle late
-            slot = grid.comm.cycle(gdt, last_cycle)
-            if slot is not None:
-                grid.dt_inflight[gdt.cycle] = ("edge", slot)
-                if deferred:
-                    gdt.update_dt(take_dt_readback(params, grid, gdt.cycle - 1))
-            return False
+    if params.use_MPI and getattr(grid.comm, "native", False) and native_cycle_usable(params):
+        # the library's own group: exchanges, sweeps and the all-reduce of the next CFL step in ONE call
+        # (armon_hip_mgpu_cycle); what is left for the host is the read-back of that scalar, one cycle late
+        grid.comm.native_cycle(gdt, last_cycle)
+        return False
     sweeps = split_axes(params.axis_splitting, gdt.cycle)
     for k, (axis, dt_factor) in enumerate(sweeps):
         # update_solver_state!: ref src/solver_state.jl:339-345
@@ -825,7 +868,7 @@ def solver_cycle(params, grid, last_cycle=True):
             # own pre-sweep c: what the reference's dtCFL_kernel reads) and, on the final
             # cycle, materialises the pre-sweep p that the reference leaves in memory.
             last = k == len(sweeps) - 1
-            sweep = fused_sweep_overlapped if params.use_MPI else fused_sweep
+            sweep = rank_sweep if params.use_MPI else fused_sweep
             sweep(params, grid, axis, dt, dx, emit_p=last and last_cycle, emit_dt=last and not params.cst_dt)
             if last and not last_cycle:
                 prefetch_halo(params, grid)
@@ -860,11 +903,11 @@ GRAPH_EVENT_SLOT = 1014    # event-pool slots 1014, 1015
 def graph_cycles_usable(params):
     """The cycle can be captured once and replayed when nothing on the host has to happen inside it: one block, fused
     sweeps, no per-cycle output (conservation print-outs, animation frames, step comparisons)."""
-    if not (params.use_fused_sweep and getattr(params, "graph_cycles", False)):
+    if not (params.use_fused_sweep and params.graph_cycles):
         return False
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
-    if not getattr(params.device, "owns_ctx", True):      # a tile context of a group: its stream is the group's, not ours to capture
+    if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
         return False
     return params.silent > 1 and params.animation_step == 0 and not params.compare and not params.kernel_callbacks
 
@@ -896,14 +939,9 @@ def time_loop_graph(params, grid, _after_handover=None):
     t1 = _time.perf_counter_ns()
     maxtime = T(params.maxtime)
 
-    def ends():
-        if params.cst_dt:
-            return T(gdt.time + gdt.current_dt) >= maxtime or gdt.cycle + 1 >= params.maxcycle
-        return gdt.cycle + 1 >= params.maxcycle or gdt.current_dt == 0 or T(gdt.time + gdt.current_dt) >= maxtime
-
     # host-driven start: cycles 0 and 1 (the second one consumes the first deferred CFL step)
     while gdt.time < maxtime and gdt.cycle < params.maxcycle and gdt.cycle < 2:
-        if solver_cycle(params, grid, last_cycle=ends()):
+        if solver_cycle(params, grid, last_cycle=cycle_ends(params, gdt)):
             break
         gdt.next_cycle()
     n_parities = 1 if params.axis_splitting in ("Sequential", "X_only", "Y_only") else 2
@@ -917,7 +955,7 @@ def time_loop_graph(params, grid, _after_handover=None):
         # with a constant time step there is no reduction to ride on and the step stays a kernel of its own
         auto = not params.cst_dt
         st = _lib.DtState(current_dt=float(gdt.current_dt), time=float(gdt.time), L_prev=float(L_prev), cycle=gdt.cycle,
-                          done=0, invalid=0, emit_p=int(ends()), auto_step=int(auto), cst_dt=int(params.cst_dt),
+                          done=0, invalid=0, emit_p=int(cycle_ends(params, gdt)), auto_step=int(auto), cst_dt=int(params.cst_dt),
                           maxcycle=params.maxcycle, cfl=float(params.cfl), maxtime=float(params.maxtime), Dt=float(params.Dt))
         state = dev.empty(C.sizeof(_lib.DtState) // 8, np.float64)
         host_state = dev.pinned(C.sizeof(_lib.DtState) // 8 * 2, np.float64)
@@ -1027,8 +1065,18 @@ def time_loop_graph(params, grid, _after_handover=None):
         grid.graph_report = {"graphs": len(graphs), "cycles_replayed": int(ran), "cycles_enqueued": cycle - start_cycle}
         host_state.free()
     params.wait()
-    t2 = _time.perf_counter_ns()
-    solve_time = t2 - t1
+    return report_run(params, gdt, _time.perf_counter_ns() - t1)
+
+
+def cycle_ends(params, gdt):
+    """Whether the cycle ``gdt`` is about to run ends the run (it then materialises p). With a variable time step the cycle's
+    dt is only known after ``next_time_step`` on cycle 0 (``current_dt == 0``): be conservative there."""
+    return (gdt.cycle + 1 >= params.maxcycle or (not params.cst_dt and gdt.current_dt == 0)
+            or params.T(gdt.time + gdt.current_dt) >= params.T(params.maxtime))
+
+
+def report_run(params, gdt, solve_time):
+    """The run summary of ref src/solver.jl:385-403 → (time, dt, cycles, cells_per_ns, solve_time_ns)."""
     cells = params.N[0] * params.N[1]
     grind_time = solve_time / max(gdt.cycle * cells, 1)
     if params.is_root and params.silent < 3:
@@ -1052,12 +1100,7 @@ def time_loop(params, grid):
     t1 = _time.perf_counter_ns()
     maxtime = params.T(params.maxtime)
     while gdt.time < maxtime and gdt.cycle < params.maxcycle:
-        if params.cst_dt:
-            ends = params.T(gdt.time + gdt.current_dt) >= maxtime or gdt.cycle + 1 >= params.maxcycle
-        else:
-            # the cycle's dt is only known after next_time_step on cycle 0: be conservative there
-            ends = (gdt.cycle + 1 >= params.maxcycle or gdt.current_dt == 0
-                    or params.T(gdt.time + gdt.current_dt) >= maxtime)
+        ends = cycle_ends(params, gdt)
         # animation frames (ref :373-378) are written after next_cycle! when (cycle - 1) % animation_step == 0; the fused
         # path only materialises p (a saved var) on request, so a cycle that ends with a frame asks for it like the last one
         frame_due = params.animation_step != 0 and gdt.cycle % params.animation_step == 0
@@ -1078,18 +1121,7 @@ def time_loop(params, grid):
                       f"|ΔM| = {dM:#8.6g}%, |ΔE| = {dE:#8.6g}%")
     drain_halo(grid)
     params.wait()   # "Last fence"
-    t2 = _time.perf_counter_ns()
-    solve_time = t2 - t1
-    cells = params.N[0] * params.N[1]
-    grind_time = solve_time / max(gdt.cycle * cells, 1)
-    if params.is_root and params.silent < 3:
-        print(" ")
-        print(f"Total time:  {solve_time / 1e9:.5f} sec")
-        print(f"Grind time:  {grind_time / 1e3:.5f} µs/cell/cycle")
-        print(f"Cells/sec:   {1 / grind_time * 1e3:.5f} Mega cells/sec")
-        print(f"Cycles:      {gdt.cycle}")
-        print(f"Last cycle:  {gdt.time:.18f} sec, Δt={gdt.current_dt:.18f} sec")
-    return float(gdt.time), float(gdt.current_dt), gdt.cycle, 1 / grind_time, solve_time
+    return report_run(params, gdt, _time.perf_counter_ns() - t1)
 
 
 def armon(params):

@@ -430,3 +430,33 @@ def test_cycle_plan_follows_split_axes(monkeypatch):
     gdt.current_dt = p.T(1e-3)
     plan, _ = cycle_plan(p, gdt, last_cycle=False, dt_host=Pinned())
     assert plan.emit_dt == 0 and plan.dt_host is None and plan.dt_event_slot == -1 and plan.overlap == 0 and plan.next_axis == -1
+
+
+def test_cycle_ends_is_the_predicate_of_every_time_loop():
+    """solver.cycle_ends = the "does this cycle end the run" expression the time loops each carried (ref src/solver.jl:
+    323-403 materialises the saved variables after the last cycle): a constant step reaching maxtime, a variable step on
+    cycle 0 (current_dt == 0: not known yet, conservatively "ends"), maxcycle hit, and the ordinary mid-run cycle."""
+    from armon_amd.solver import cycle_ends
+
+    def expected(p, gdt):       # the expressions of time_loop, time_loop_graph and TileGroup.time_loop
+        maxtime = p.T(p.maxtime)
+        if p.cst_dt:
+            return p.T(gdt.time + gdt.current_dt) >= maxtime or gdt.cycle + 1 >= p.maxcycle
+        return gdt.cycle + 1 >= p.maxcycle or gdt.current_dt == 0 or p.T(gdt.time + gdt.current_dt) >= maxtime
+
+    for dtype in ("float64", "float32"):
+        cst = ArmonParameters(test="Sod", N=(16, 16), cst_dt=True, Dt=0.25, maxtime=1.0, maxcycle=100, data_type=dtype)
+        var = ArmonParameters(test="Sod", N=(16, 16), maxtime=1.0, maxcycle=10, data_type=dtype)
+        cases = [(cst, 1, 0.5, 0.25, False),          # mid-run, constant step
+                 (cst, 3, 0.75, 0.25, True),          # cst_dt reaching maxtime exactly
+                 (cst, 99, 0.5, 0.25, True),          # maxcycle hit
+                 (var, 0, 0.0, 0.0, True),            # variable dt on cycle 0: conservative
+                 (var, 4, 0.3, 0.01, False),          # the ordinary mid-run cycle
+                 (var, 4, 0.995, 0.01, True),         # this step crosses maxtime
+                 (var, 9, 0.3, 0.01, True)]           # maxcycle hit
+        for p, cycle, time, dt, want in cases:
+            gdt = GlobalTimeStep(p)
+            gdt.cycle, gdt.time, gdt.current_dt = cycle, p.T(time), p.T(dt)
+            assert cycle_ends(p, gdt) == expected(p, gdt) == want, (dtype, cycle, time, dt)
+    gdt = GlobalTimeStep(cst)                 # a fresh constant-step run starts with current_dt = Dt, not 0
+    assert gdt.current_dt == cst.T(0.25) and not cycle_ends(cst, gdt)
