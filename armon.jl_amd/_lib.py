@@ -138,6 +138,8 @@ SIGNATURES = {
                                   _dbl, C.POINTER(BlockDataPtrs)]),
     "armon_hip_coarsen": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 6),
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),
+    "armon_hip_state_pack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
+    "armon_hip_state_unpack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
     "armon_hip_sweep": (_ci, [_vp, C.POINTER(SweepDesc)]),
     "armon_hip_dt_state_step": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
     "armon_hip_dt_state_step_f32": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
@@ -185,7 +187,7 @@ def _add_f32_signatures():
     for name in ("perfect_gas_EOS", "bizarrium_EOS", "acoustic", "acoustic_GAD", "cell_update",
                  "advection_first_order", "advection_second_order", "euler_projection", "boundary_conditions",
                  "pack_to_array", "unpack_from_array", "dtCFL_async", "dtCFL", "conservation_vars", "init_test",
-                 "coarsen", "gather_strided"):
+                 "coarsen", "gather_strided", "state_pack", "state_unpack"):
         res, args = SIGNATURES["armon_hip_" + name]
         conv = []
         for a in args:

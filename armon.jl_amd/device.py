@@ -210,6 +210,14 @@ class PinnedArray:
         check(self.device._L.armon_hip_memcpy_async(self.device.ctx, C.c_void_p(self.ptr + dst_offset * sz),
                                                     C.c_void_p(src.ptr + src_offset * sz), n * sz, _lib_kind("D2H")))
 
+    def copy_to_device_async(self, dst, n=None, src_offset=0, dst_offset=0):
+        """Enqueue an H2D copy of ``n`` elements on the context's stream; the caller orders the reuse of the source with an
+        event."""
+        n = len(dst) - dst_offset if n is None else n
+        sz = self.dtype.itemsize
+        check(self.device._L.armon_hip_memcpy_async(self.device.ctx, C.c_void_p(dst.ptr + dst_offset * sz),
+                                                    C.c_void_p(self.ptr + src_offset * sz), n * sz, _lib_kind("H2D")))
+
     def free(self):
         if self.ptr and self.device.ctx:
             self.array = None

@@ -299,17 +299,30 @@ class TileGroup(NativeGroup):
     def time_loop(self):
         """ref src/solver.jl:323-403"""
         p0, gdt = self.root, self.global_dt
+        from .checkpoint import checkpoint_path
         gdt.reset()
         self.dt_inflight.clear()
+        if p0.restart_from is not None:
+            self.load_state(p0.restart_from)
         self.wait()
         t1 = _time.perf_counter_ns()
         maxtime = p0.T(p0.maxtime)
+        saved_at, save_ns = -1, 0         # checkpoints are disk I/O: their time is taken out of the solve time
         while gdt.time < maxtime and gdt.cycle < p0.maxcycle:
             self.solver_cycle(last_cycle=S.cycle_ends(p0, gdt))
             gdt.next_cycle()
+            if p0.checkpoint_step != 0 and gdt.cycle % p0.checkpoint_step == 0:
+                self.wait()
+                t_save = _time.perf_counter_ns()
+                self.save_state(checkpoint_path(p0, gdt.cycle))
+                save_ns += _time.perf_counter_ns() - t_save
+                saved_at = gdt.cycle
         self.drain()
         self.wait()
-        return _time.perf_counter_ns() - t1
+        solve_ns = _time.perf_counter_ns() - t1 - save_ns
+        if p0.checkpoint_at_end and saved_at != gdt.cycle:
+            self.save_state(checkpoint_path(p0, gdt.cycle))
+        return solve_ns
 
     def run(self):
         """``armon(params)`` for the whole group → SolverStats (``data`` = this group)."""
@@ -319,6 +332,28 @@ class TileGroup(NativeGroup):
         cells = g[0] * g[1]
         return S.SolverStats(float(gdt.time), float(gdt.current_dt), gdt.cycle, solve_ns / 1e9, cells,
                              gdt.cycle * cells / max(solve_ns, 1), data=self)
+
+    # ---- checkpoint / restart (checkpoint.py) ---------------------------------------------------------------------
+    def _tiles_at_rest(self):
+        """Every tile with nothing of the group in flight: an exchange posted ahead is completed (the next cycle then posts its
+        own, as at cycle 0) and all streams are idle."""
+        self.drain()
+        self.wait()
+        return list(zip(self.params, self.grids))
+
+    def state_digest(self, names=S.STATE_VARS):
+        """``BlockGrid.state_digest`` of the whole domain: the sum mod 2^64 of the tiles' digests = the single block's."""
+        from . import checkpoint
+        return checkpoint.state_digest(self._tiles_at_rest(), tuple(names))
+
+    def save_state(self, path, band_rows=None):
+        """Each tile writes its window of the GLOBAL planes: the file is byte-identical to the single block's."""
+        from . import checkpoint
+        return checkpoint.save(self._tiles_at_rest(), self.global_dt, self.dt, path, band_rows=band_rows)
+
+    def load_state(self, path, band_rows=None):
+        from . import checkpoint
+        return checkpoint.load(self._tiles_at_rest(), self.global_dt, self.dt, path, band_rows=band_rows)
 
     def gather(self, names=("rho", "u", "v", "E", "p")):
         """The real cells of every tile assembled into global (NY, NX) arrays on the host."""

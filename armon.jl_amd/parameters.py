@@ -5,6 +5,8 @@ consumes its own options and anything left over is an error (ref src/parameters.
 that only steer the reference's CPU machinery (threads, NUMA, cache blocking, logging) are accepted and
 recorded so that a reference script runs unchanged, but have no effect on the device path.
 """
+import numbers
+
 import numpy as np
 
 from ._lib import solver_error
@@ -214,8 +216,26 @@ class ArmonParameters:
     def _init_output(self, silent=0, output_dir=".", output_file="output", write_output=False,
                      write_ghosts=False, write_slices=False, output_precision=None, animation_step=0,
                      compare=False, is_ref=False, comparison_tolerance=1e-10, check_result=False,
-                     return_data=False, **options):
+                     return_data=False, checkpoint_step=0, checkpoint_file="checkpoint", checkpoint_at_end=False,
+                     restart_from=None, **options):
+        """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
+        ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
+        ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart)."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
+        if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
+            solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
+        self.checkpoint_step = int(checkpoint_step)
+        self.checkpoint_file = str(checkpoint_file)
+        if not self.checkpoint_file or "/" in self.checkpoint_file:
+            solver_error("config", f"checkpoint_file is a file name inside output_dir, got {checkpoint_file!r}")
+        self.checkpoint_at_end = bool(checkpoint_at_end)
+        self.restart_from = None if restart_from is None else str(restart_from)
+        if self.restart_from is not None and (self.compare or self.is_ref):
+            solver_error("config", "restart_from cannot be combined with compare / is_ref: the step files of a reference "
+                                   "run start at cycle 0")
+        if self.use_MPI and (self.checkpoint_step or self.checkpoint_at_end or self.restart_from is not None):
+            solver_error("config", "checkpoint / restart is not supported for ranks of a process group (use_MPI=true): "
+                                   "one block or an in-process tile group only")
         self.comparison_tolerance = float(comparison_tolerance)
         self.silent = silent
         self.output_dir, self.output_file = output_dir, output_file
@@ -365,8 +385,6 @@ def cart_neighbours(coords, dims, periodic=(False, False)):
 
 def normalize_coarsen_factor(factor):
     """``0 | f | (fx, fy)`` -> ``None`` (no coarsening) or a pair of integers >= 1; anything else is a configuration error."""
-    import numbers
-
     def integer(f):
         if isinstance(f, bool) or not isinstance(f, (numbers.Integral, np.integer)):
             solver_error("config", f"coarsening factors must be integers, got {f!r}")

@@ -363,6 +363,24 @@ class BlockGrid:
         res["x"], res["y"] = self.coarse_coordinates(factor)
         return res
 
+    def state_digest(self, names=STATE_VARS):
+        """64-bit digest of the real cells of each vector of ``names`` (at most 8), computed on the device
+        (armon_hip_state_pack without a destination; checkpoint.py states the formula) → tuple of ints. A function of the
+        values and their GLOBAL positions only: ghost cells, ghost width and decomposition do not enter, and the digests of
+        the tiles of a group add up (mod 2^64) to the single block's."""
+        from . import checkpoint
+        return checkpoint.state_digest([(self.params, self)], tuple(names))
+
+    def save_state(self, path, band_rows=None):
+        """Write a checkpoint of this block (checkpoint.py) → its header."""
+        from . import checkpoint
+        return checkpoint.save([(self.params, self)], self.global_dt, self.dt, path, band_rows=band_rows)
+
+    def load_state(self, path, band_rows=None):
+        """Load the state, the clock and the pending CFL step of a checkpoint over this (initialised) block → its header."""
+        from . import checkpoint
+        return checkpoint.load([(self.params, self)], self.global_dt, self.dt, path, band_rows=band_rows)
+
     def host_to_device(self, host):
         for f, a in host.items():
             self.data[f].copy_from_host(a)
@@ -799,6 +817,14 @@ class DtReadback:
         check(self.params.device._L.armon_hip_event_sync(self.inflight.pop(cycle), DT_EVENT_SLOT + (cycle & 1)))
         return float(self.host.array[cycle & 1])
 
+    def prime(self, cycle, value):
+        """Make ``value`` the CFL step posted by ``cycle``, already landed (a restart, or a checkpoint that took it to store
+        it): the pinned slot holds it and the slot's event, recorded now on the compute stream, is what ``take`` waits for."""
+        dev = self.params.device
+        self.landing().array[cycle & 1] = value
+        dev.event_record(DT_EVENT_SLOT + (cycle & 1))
+        self.inflight[cycle] = dev.ctx
+
     def free(self):
         if self.host is not None:
             self.host.free()
@@ -905,6 +931,8 @@ def graph_cycles_usable(params):
     sweeps, no per-cycle output (conservation print-outs, animation frames, step comparisons)."""
     if not (params.use_fused_sweep and params.graph_cycles):
         return False
+    if params.checkpoint_step != 0 or params.checkpoint_at_end or params.restart_from is not None:
+        return False                    # checkpoints are written, and a restart is primed, between host-driven cycles
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
@@ -1096,9 +1124,12 @@ def time_loop(params, grid):
     grid.global_dt.reset()
     grid.dt_inflight.clear()
     gdt = grid.global_dt
+    if params.restart_from is not None:
+        grid.load_state(params.restart_from)
     params.wait()
     t1 = _time.perf_counter_ns()
     maxtime = params.T(params.maxtime)
+    saved_at, save_ns = -1, 0             # checkpoints are disk I/O: their time is taken out of the solve time
     while gdt.time < maxtime and gdt.cycle < params.maxcycle:
         ends = cycle_ends(params, gdt)
         # animation frames (ref :373-378) are written after next_cycle! when (cycle - 1) % animation_step == 0; the fused
@@ -1119,9 +1150,20 @@ def time_loop(params, grid):
                 dE = abs(params.initial_energy - energy) / params.initial_energy * 100
                 print(f"Cycle {gdt.cycle:4d}: dt = {gdt.current_dt:.18f}, t = {gdt.time:.18f}, "
                       f"|ΔM| = {dM:#8.6g}%, |ΔE| = {dE:#8.6g}%")
+        if params.checkpoint_step != 0 and gdt.cycle % params.checkpoint_step == 0:
+            from .checkpoint import checkpoint_path
+            params.wait()
+            t_save = _time.perf_counter_ns()
+            grid.save_state(checkpoint_path(params, gdt.cycle))
+            save_ns += _time.perf_counter_ns() - t_save
+            saved_at = gdt.cycle
     drain_halo(grid)
     params.wait()   # "Last fence"
-    return report_run(params, gdt, _time.perf_counter_ns() - t1)
+    solve_ns = _time.perf_counter_ns() - t1 - save_ns
+    if params.checkpoint_at_end and saved_at != gdt.cycle:
+        from .checkpoint import checkpoint_path
+        grid.save_state(checkpoint_path(params, gdt.cycle))
+    return report_run(params, gdt, solve_ns)
 
 
 def armon(params):

@@ -250,6 +250,28 @@ ARMON_API int armon_hip_coarsen(armon_ctx*, int64_t row_length, int nghost, int6
 ARMON_API int armon_hip_gather_strided(armon_ctx*, int64_t n_cells, int nvars, const double* const* vars,
         int64_t start, int64_t stride, int64_t count, double* out_dev);
 
+/* ---- checkpoint / restart (no reference counterpart; csrc/checkpoint.hip) ---- */
+/* Move a window of REAL cells between the vectors of one block and a dense buffer, and digest it, in one pass. The block has
+ * rows of `row_length` elements, `nghost` ghost layers and nx x ny real cells; the window is the real cells
+ * [col0, col0 + wnx) x [row0, row0 + wny) and may not leave the real domain; no ghost cell is read or written. `vars` = HOST
+ * array of `nvars` <= 8 device pointers; the dense side is [nvars][wny][wnx] in device memory. `global_first` = global 0-based
+ * index gy * global_nx + gx of the window's first cell, `global_nx` the global row length.
+ * state_pack: vectors -> dense (`dense_dev` NULL = digest only); state_unpack: dense -> vectors (digest of what it wrote).
+ * Both ADD to `digest_dev[k]` (device, one 64-bit word per variable, cleared by the caller) the sum mod 2^64 over the cells of
+ *     mix64(b + mix64(8 g + k + 1)),   b = the value's bit pattern zero-extended to 64 bits, g = its global index,
+ *     mix64(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31
+ * — a function of the values and their global positions only, so the digests of the parts of a domain add up to the
+ * digest of the domain whatever the split. Async on the context's stream, no atomics. One partial per workgroup and variable
+ * goes through the context's reduction scratch (8 x 8 x CUs words at most): like every reduction of this library the call
+ * synchronises the stream ONCE if that scratch has to grow, and is refused (ARMON_ERR_INVALID_ARG) when it would have to grow
+ * inside a stream capture or while a captured graph of the context is alive. Otherwise no host synchronisation. */
+ARMON_API int armon_hip_state_pack(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
+        const double* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
+        int64_t global_nx, double* dense_dev, uint64_t* digest_dev);
+ARMON_API int armon_hip_state_unpack(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
+        double* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
+        int64_t global_nx, const double* dense_dev, uint64_t* digest_dev);
+
 /* ---- fp32 variants (ref data_type=Float32, src/parameters.jl:185): same kernels, float arrays and scalars ---- */
 typedef struct {
     float *x, *y, *rho, *u, *v, *E, *p, *c, *g, *us, *ps, *work_1, *work_2, *work_3, *work_4, *mask;
@@ -293,6 +315,12 @@ ARMON_API int armon_hip_coarsen_f32(armon_ctx*, int64_t row_length, int nghost, 
         const float* rho, const float* u, const float* v, const float* E, const float* p, float* out_dev);
 ARMON_API int armon_hip_gather_strided_f32(armon_ctx*, int64_t n_cells, int nvars, const float* const* vars,
         int64_t start, int64_t stride, int64_t count, float* out_dev);
+ARMON_API int armon_hip_state_pack_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
+        const float* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
+        int64_t global_nx, float* dense_dev, uint64_t* digest_dev);
+ARMON_API int armon_hip_state_unpack_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
+        float* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
+        int64_t global_nx, const float* dense_dev, uint64_t* digest_dev);
 
 /* ---- fused sweep: EOS → BC (in-tile mirror) → fluxes → cell update → advection → projection ---- */
 /* One call = one directional sweep of solver_cycle (ref src/solver.jl:300-316) over one block, reading
