@@ -68,6 +68,12 @@ class DtState(C.Structure):
                 ("cfl", C.c_double), ("maxtime", C.c_double), ("Dt", C.c_double)]
 
 
+class StateDiff(C.Structure):
+    """armon_state_diff — what separates two states, per variable (include/armon_hip.h, armon_hip_state_compare)."""
+    _fields_ = [(f, C.c_uint64) for f in ("n_cells", "n_bits", "n_out", "first_out", "max_abs", "max_abs_at", "max_rel",
+                                          "max_rel_at")]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -140,6 +146,8 @@ SIGNATURES = {
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),
     "armon_hip_state_pack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
     "armon_hip_state_unpack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
+    "armon_hip_state_diff_reset": (_ci, [_vp, _ci, _dp]),
+    "armon_hip_state_compare": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dbl, _dbl, _dp, _dp]),
     "armon_hip_sweep": (_ci, [_vp, C.POINTER(SweepDesc)]),
     "armon_hip_dt_state_step": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
     "armon_hip_dt_state_step_f32": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
@@ -204,6 +212,7 @@ def _add_f32_signatures():
                  "halo_exchange_finish_edge", "mgpu_edge_join", "mgpu_cycle", "mgpu_drain"):
         SIGNATURES["armon_hip_" + name + "_f32"] = SIGNATURES["armon_hip_" + name]
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
+    SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
     SIGNATURES["armon_hip_tune_placement_f32"] = SIGNATURES["armon_hip_tune_placement"]
     SIGNATURES["armon_hip_choose_placement_f32"] = SIGNATURES["armon_hip_choose_placement"]
 

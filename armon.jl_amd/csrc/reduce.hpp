@@ -15,12 +15,24 @@ struct op_min { template <typename T> __device__ static T id() { return T(INFINI
 // reach the host's validity check (ref src/solver_state.jl:123-124)
 struct op_max { template <typename T> __device__ static T id() { return T(0.); } template <typename T> __device__ static T f(T a, T b) { return phys::amax(a, b); } };
 struct op_sum { template <typename T> __device__ static T id() { return T(0.); } template <typename T> __device__ static T f(T a, T b) { return a + b; } };
+// minimum of unsigned integers (positions; the all-ones word = none)
+struct op_umin { template <typename T> __device__ static T id() { return ~T(0); } template <typename T> __device__ static T f(T a, T b) { return b < a ? b : a; } };
+// (value, position) pairs of unsigned 64-bit words: the larger value wins, on equal values the smaller position. Associative
+// and commutative; the neutral element is (0, all ones), which is also what a value of 0 carries as its position.
+struct upair { unsigned long long v, at; };
+struct op_pair_max {
+    template <typename T> __device__ static T id() { return T{0ull, ~0ull}; }
+    template <typename T> __device__ static T f(T a, T b) { return (b.v > a.v || (b.v == a.v && b.at < a.at)) ? b : a; }
+};
+
+template <typename T> __device__ __forceinline__ T shfl_down(T v, int off) { return __shfl_down(v, off, kWave); }
+__device__ __forceinline__ upair shfl_down(upair p, int off) { return upair{__shfl_down(p.v, off, kWave), __shfl_down(p.at, off, kWave)}; }
 
 template <typename OP, typename T>
 __device__ __forceinline__ T wave_reduce(T v)
 {
 #pragma unroll
-    for (int off = kWave / 2; off > 0; off >>= 1) v = OP::f(v, __shfl_down(v, off, kWave));
+    for (int off = kWave / 2; off > 0; off >>= 1) v = OP::f(v, shfl_down(v, off));
     return v;   // valid in lane 0
 }
 

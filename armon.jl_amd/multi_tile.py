@@ -308,6 +308,8 @@ class TileGroup(NativeGroup):
         t1 = _time.perf_counter_ns()
         maxtime = p0.T(p0.maxtime)
         saved_at, save_ns = -1, 0         # checkpoints are disk I/O: their time is taken out of the solve time
+        compared_at, stopped = -1, False  # (and so is the time of the comparisons with a reference run's checkpoints)
+        self.state_diffs = []
         while gdt.time < maxtime and gdt.cycle < p0.maxcycle:
             self.solver_cycle(last_cycle=S.cycle_ends(p0, gdt))
             gdt.next_cycle()
@@ -317,11 +319,23 @@ class TileGroup(NativeGroup):
                 self.save_state(checkpoint_path(p0, gdt.cycle))
                 save_ns += _time.perf_counter_ns() - t_save
                 saved_at = gdt.cycle
+            if p0.compare_step != 0 and gdt.cycle % p0.compare_step == 0:
+                from .compare import compare_run
+                self.wait()
+                t_save = _time.perf_counter_ns()
+                stopped = compare_run(self, p0, gdt)
+                save_ns += _time.perf_counter_ns() - t_save
+                compared_at = gdt.cycle
+                if stopped:
+                    break                 # the first difference ends the run (ref @checkpoint, src/solver.jl:40-55)
         self.drain()
         self.wait()
         solve_ns = _time.perf_counter_ns() - t1 - save_ns
         if p0.checkpoint_at_end and saved_at != gdt.cycle:
             self.save_state(checkpoint_path(p0, gdt.cycle))
+        if p0.compare_at_end and compared_at != gdt.cycle and not stopped:
+            from .compare import compare_run
+            compare_run(self, p0, gdt)
         return solve_ns
 
     def run(self):
@@ -331,7 +345,7 @@ class TileGroup(NativeGroup):
         gdt, g = self.global_dt, self.root.global_grid
         cells = g[0] * g[1]
         return S.SolverStats(float(gdt.time), float(gdt.current_dt), gdt.cycle, solve_ns / 1e9, cells,
-                             gdt.cycle * cells / max(solve_ns, 1), data=self)
+                             gdt.cycle * cells / max(solve_ns, 1), data=self, state_diffs=list(self.state_diffs))
 
     # ---- checkpoint / restart (checkpoint.py) ---------------------------------------------------------------------
     def _tiles_at_rest(self):
@@ -354,6 +368,11 @@ class TileGroup(NativeGroup):
     def load_state(self, path, band_rows=None):
         from . import checkpoint
         return checkpoint.load(self._tiles_at_rest(), self.global_dt, self.dt, path, band_rows=band_rows)
+
+    def compare_state(self, ref, rtol=None, atol=0.0, names=None, limit=20, band_rows=None):
+        """``BlockGrid.compare_state`` of the whole domain: the merge of the tiles' records = the single block's."""
+        from . import compare
+        return compare.compare_state(self._tiles_at_rest(), ref, rtol=rtol, atol=atol, names=names, limit=limit, band_rows=band_rows)
 
     def gather(self, names=("rho", "u", "v", "E", "p")):
         """The real cells of every tile assembled into global (NY, NX) arrays on the host."""

@@ -217,10 +217,17 @@ class ArmonParameters:
                      write_ghosts=False, write_slices=False, output_precision=None, animation_step=0,
                      compare=False, is_ref=False, comparison_tolerance=1e-10, check_result=False,
                      return_data=False, checkpoint_step=0, checkpoint_file="checkpoint", checkpoint_at_end=False,
-                     restart_from=None, **options):
+                     restart_from=None, compare_step=0, compare_dir=None, compare_file="checkpoint", compare_at_end=False,
+                     comparison_atol=0.0, comparison_time_atol=0.0, **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
-        ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart)."""
+        ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart).
+        ``compare_step=k``: after every k completed cycles (0 = off) the state is compared on the device with
+        ``<compare_dir>/<compare_file>_<cycle:06d>.ckpt`` — the checkpoints of a reference run — within ``comparison_tolerance``
+        (relative) and ``comparison_atol`` (a number, or a dict plane → number); the file's time is compared with the run's
+        within ``comparison_tolerance`` and ``comparison_time_atol``; ``compare_at_end``: with the file of the final cycle;
+        the first difference is reported and stops the run (compare.py; the text ``compare`` / ``is_ref`` path is untouched by
+        these)."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
         if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
             solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
@@ -237,6 +244,32 @@ class ArmonParameters:
             solver_error("config", "checkpoint / restart is not supported for ranks of a process group (use_MPI=true): "
                                    "one block or an in-process tile group only")
         self.comparison_tolerance = float(comparison_tolerance)
+        if isinstance(compare_step, bool) or not isinstance(compare_step, (numbers.Integral, np.integer)) or compare_step < 0:
+            solver_error("config", f"compare_step must be an integer >= 0, got {compare_step!r}")
+        self.compare_step = int(compare_step)
+        self.compare_dir = None if compare_dir is None else str(compare_dir)
+        self.compare_file = str(compare_file)
+        if not self.compare_file or "/" in self.compare_file:
+            solver_error("config", f"compare_file is a file name inside compare_dir, got {compare_file!r}")
+        self.compare_at_end = bool(compare_at_end)
+        atols = list(comparison_atol.values()) if isinstance(comparison_atol, dict) else [comparison_atol]
+        if not all(isinstance(v, (numbers.Real, np.floating)) and not isinstance(v, bool) and v >= 0 for v in atols):
+            solver_error("config", f"comparison_atol must be a number >= 0 (or a dict plane -> number), got {comparison_atol!r}")
+        self.comparison_atol = ({str(k): float(v) for k, v in comparison_atol.items()} if isinstance(comparison_atol, dict)
+                                else float(comparison_atol))
+        if isinstance(comparison_time_atol, bool) or not isinstance(comparison_time_atol, (numbers.Real, np.floating)) \
+                or not comparison_time_atol >= 0:
+            solver_error("config", f"comparison_time_atol must be a number >= 0, got {comparison_time_atol!r}")
+        self.comparison_time_atol = float(comparison_time_atol)
+        self.state_compare = self.compare_step != 0 or self.compare_at_end      # any comparison with checkpoints during the run
+        if (self.state_compare or self.compare_dir is not None) and (self.compare or self.is_ref):
+            solver_error("config", "compare_step / compare_at_end / compare_dir cannot be combined with compare / is_ref: "
+                                   "one compares with checkpoints on the device, the other with text files per sub-step")
+        if (self.state_compare or self.compare_dir is not None) and self.use_MPI:
+            solver_error("config", "compare_step / compare_at_end are not supported for ranks of a process group (use_MPI=true): "
+                                   "one block or an in-process tile group only")
+        if self.state_compare and self.compare_dir is None:
+            solver_error("config", "compare_step / compare_at_end need compare_dir: the directory of the reference run's checkpoints")
         self.silent = silent
         self.output_dir, self.output_file = output_dir, output_file
         self.write_output, self.write_ghosts = write_output, write_ghosts

@@ -9,7 +9,7 @@ through the C ABI of libarmon_hip.so; nothing here computes on the host.
 import ctypes as C
 import math
 import time as _time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -35,6 +35,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     data: object = None
     timer: object = None
     grid_log: object = None
+    state_diffs: list = field(default_factory=list)     # (cycle, compare.StateDiff) of compare_step / compare_at_end
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -163,6 +164,7 @@ class BlockGrid:
         self.comm = None                       # set by halo_exchange.setup when use_MPI
         self.halo_prefetch = None              # (axis, handle) of an exchange posted ahead of its sweep
         self._coarse_xy = {}                   # (fx, fy) -> coordinates of the coarse cells (coarse_coordinates)
+        self.state_diffs = []                  # (cycle, StateDiff) of the run's compare_step / compare_at_end
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -386,6 +388,12 @@ class BlockGrid:
             self.data[f].copy_from_host(a)
         if "x" in host or "y" in host:
             self._coarse_xy.clear()
+
+    def compare_state(self, ref, rtol=None, atol=0.0, names=None, limit=20, band_rows=None):
+        """What separates this block's state from ``ref`` — a checkpoint's path, or a ``BlockGrid`` / ``TileGroup`` of the same
+        global grid and data type — computed on the device (compare.py) → ``compare.StateDiff``."""
+        from . import compare
+        return compare.compare_state([(self.params, self)], ref, rtol=rtol, atol=atol, names=names, limit=limit, band_rows=band_rows)
 
     def real_view(self, a):
         g = self.size.ghosts
@@ -933,6 +941,8 @@ def graph_cycles_usable(params):
         return False
     if params.checkpoint_step != 0 or params.checkpoint_at_end or params.restart_from is not None:
         return False                    # checkpoints are written, and a restart is primed, between host-driven cycles
+    if params.state_compare or params.compare_dir is not None:
+        return False                    # and so is a state compared with a reference run's checkpoint
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
@@ -1130,6 +1140,8 @@ def time_loop(params, grid):
     t1 = _time.perf_counter_ns()
     maxtime = params.T(params.maxtime)
     saved_at, save_ns = -1, 0             # checkpoints are disk I/O: their time is taken out of the solve time
+    compared_at, stopped = -1, False      # (and so is the time of the comparisons with a reference run's checkpoints)
+    grid.state_diffs = []
     while gdt.time < maxtime and gdt.cycle < params.maxcycle:
         ends = cycle_ends(params, gdt)
         # animation frames (ref :373-378) are written after next_cycle! when (cycle - 1) % animation_step == 0; the fused
@@ -1157,12 +1169,24 @@ def time_loop(params, grid):
             grid.save_state(checkpoint_path(params, gdt.cycle))
             save_ns += _time.perf_counter_ns() - t_save
             saved_at = gdt.cycle
+        if params.compare_step != 0 and gdt.cycle % params.compare_step == 0:
+            from .compare import compare_run
+            params.wait()
+            t_save = _time.perf_counter_ns()
+            stopped = compare_run(grid, params, gdt)
+            save_ns += _time.perf_counter_ns() - t_save
+            compared_at = gdt.cycle
+            if stopped:
+                break                     # the first difference ends the run (ref @checkpoint, src/solver.jl:40-55)
     drain_halo(grid)
     params.wait()   # "Last fence"
     solve_ns = _time.perf_counter_ns() - t1 - save_ns
     if params.checkpoint_at_end and saved_at != gdt.cycle:
         from .checkpoint import checkpoint_path
         grid.save_state(checkpoint_path(params, gdt.cycle))
+    if params.compare_at_end and compared_at != gdt.cycle and not stopped:
+        from .compare import compare_run
+        compare_run(grid, params, gdt)
     return report_run(params, gdt, solve_ns)
 
 
@@ -1195,6 +1219,7 @@ def armon(params):
         from .io import write_slices_files
         write_slices_files(params, grid, params.output_file)
     stats = SolverStats(final_time, dt, cycles, solve_time / 1e9, params.N[0] * params.N[1], cells_per_ns)
+    stats.state_diffs = list(grid.state_diffs)
     if params.return_data:
         stats.data = grid
     return stats

@@ -272,6 +272,51 @@ ARMON_API int armon_hip_state_unpack(armon_ctx*, int64_t row_length, int nghost,
         double* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
         int64_t global_nx, const double* dense_dev, uint64_t* digest_dev);
 
+/* ---- state comparison on the device (no reference counterpart; csrc/state_compare.hip) ---- */
+/* What separates two states, per variable: 64 bytes, every field MERGES (counts add, first_out is a minimum, a (value, position)
+ * pair takes the larger bit pattern and on equal patterns the smaller position), so the record of a domain is the merge of
+ * the records of its parts whatever the split, and does not depend on the launch shape, the alignment, the ghost width or the
+ * decomposition. Positions are GLOBAL 0-based indices g = gy * global_nx + gx. */
+typedef struct {
+    uint64_t n_cells;       /* cells compared                                                          (sum) */
+    uint64_t n_bits;        /* cells whose bit patterns differ                                         (sum) */
+    uint64_t n_out;         /* cells outside the tolerance                                             (sum) */
+    uint64_t first_out;     /* smallest g of such a cell, UINT64_MAX = none                            (min) */
+    uint64_t max_abs;       /* bit pattern, zero-extended, of the largest d                            (pair max) */
+    uint64_t max_abs_at;    /* smallest g that attains it; UINT64_MAX while max_abs == 0 */
+    uint64_t max_rel;       /* the same for d / m                                                      (pair max) */
+    uint64_t max_rel_at;
+} armon_state_diff;
+
+/* Write the neutral element of the merge (zeros, positions UINT64_MAX) into diff_dev[0 .. nvars), 1 <= nvars <= 8. Async. */
+ARMON_API int armon_hip_state_diff_reset(armon_ctx*, int nvars, armon_state_diff* diff_dev);
+
+/* Compare the window of REAL cells [col0, col0 + wnx) x [row0, row0 + wny) of the `nvars` <= 8 vectors of one block with the
+ * dense reference `ref_dense_dev` = [nvars][wny][wnx] (device memory) and MERGE the result into diff_dev[0 .. nvars). Block,
+ * window, `vars`, `global_first`, `global_nx` and their checks are those of armon_hip_state_pack; in addition `ref_dense_dev`
+ * and `diff_dev` must not be NULL and rtol, atol must be >= 0 and not NaN (ARMON_ERR_INVALID_ARG otherwise, nothing written).
+ * Per cell, a = the vector's value, b = the reference's, all arithmetic in the data type (rtol, atol converted to it on the
+ * host), no contraction, correctly rounded division:
+ *     same = (a == b) or both are NaN:  d = 0 and the relative difference is 0   (equal infinities included);
+ *     otherwise  d = |a - b|,  m = max(|a|, |b|),  relative difference = d / m;
+ *     within tolerance = same, or both finite and d <= max(atol, rtol * m)
+ * — Julia's isapprox as the reference's tests use it, two NaNs counted as equal. A cell counts for n_bits when the bit
+ * patterns differ (-0.0 against +0.0: n_bits, not n_out). A NaN in d or d / m enters the maxima as the canonical quiet NaN
+ * (0x7ff8000000000000 / 0x7fc00000): the unsigned maximum of bit patterns is then sticky and unique.
+ * `row_out_dev` (device, [nvars][wny] 32-bit words zeroed by the caller, or NULL): row_out_dev[q * wny + r] += the cells of
+ * window row r of variable q that are outside the tolerance (integer atomic add: order-independent).
+ * No ghost cell is read, nothing outside the dense window is read, nothing is written except diff_dev, row_out_dev and the
+ * context's reduction scratch (7 x 8 x CUs words at most), which grows as in armon_hip_state_pack: one stream synchronisation
+ * the first time, refused inside a stream capture or while a captured graph of the context is alive. Async on the stream. */
+ARMON_API int armon_hip_state_compare(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
+        const double* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
+        int64_t global_nx, const double* ref_dense_dev, double rtol, double atol, armon_state_diff* diff_dev,
+        uint32_t* row_out_dev);
+ARMON_API int armon_hip_state_compare_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
+        const float* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
+        int64_t global_nx, const float* ref_dense_dev, double rtol, double atol, armon_state_diff* diff_dev,
+        uint32_t* row_out_dev);
+
 /* ---- fp32 variants (ref data_type=Float32, src/parameters.jl:185): same kernels, float arrays and scalars ---- */
 typedef struct {
     float *x, *y, *rho, *u, *v, *E, *p, *c, *g, *us, *ps, *work_1, *work_2, *work_3, *work_4, *mask;
