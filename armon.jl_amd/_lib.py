@@ -74,6 +74,20 @@ class StateDiff(C.Structure):
                                           "max_rel_at")]
 
 
+class ProfileBin(C.Structure):
+    """armon_profile_bin — one bin of a profile, 24 words (include/armon_hip.h, armon_hip_profile)."""
+    _fields_ = [("n", C.c_uint64), ("n_bad", C.c_uint64), ("sum", (C.c_int64 * 3) * 5),
+                ("rho_min", C.c_uint64), ("rho_max", C.c_uint64), ("p_min", C.c_uint64), ("p_max", C.c_uint64),
+                ("reserved", C.c_uint64 * 3)]
+
+
+class ProfileSpec(C.Structure):
+    """armon_profile_spec — what a profile bins by, and the quanta of its sums."""
+    _fields_ = [("kind", C.c_int32), ("eos", C.c_int32), ("nbins", C.c_int64), ("width", C.c_int64),
+                ("cx", C.c_double), ("cy", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("inv_dr", C.c_double),
+                ("gamma", C.c_double), ("scale_exp", C.c_int32 * 5)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -148,6 +162,9 @@ SIGNATURES = {
     "armon_hip_state_unpack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
     "armon_hip_state_diff_reset": (_ci, [_vp, _ci, _dp]),
     "armon_hip_state_compare": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dbl, _dbl, _dp, _dp]),
+    "armon_hip_profile_reset": (_ci, [_vp, _i64, _dp]),
+    "armon_hip_profile": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ProfileSpec), _dp]),
+    "armon_hip_profile_bounds": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ProfileSpec), _dp]),
     "armon_hip_sweep": (_ci, [_vp, C.POINTER(SweepDesc)]),
     "armon_hip_dt_state_step": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
     "armon_hip_dt_state_step_f32": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
@@ -213,6 +230,8 @@ def _add_f32_signatures():
         SIGNATURES["armon_hip_" + name + "_f32"] = SIGNATURES["armon_hip_" + name]
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
+    SIGNATURES["armon_hip_profile_f32"] = SIGNATURES["armon_hip_profile"]
+    SIGNATURES["armon_hip_profile_bounds_f32"] = SIGNATURES["armon_hip_profile_bounds"]
     SIGNATURES["armon_hip_tune_placement_f32"] = SIGNATURES["armon_hip_tune_placement"]
     SIGNATURES["armon_hip_choose_placement_f32"] = SIGNATURES["armon_hip_choose_placement"]
 

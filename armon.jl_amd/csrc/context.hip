@@ -121,6 +121,7 @@ int armon_hip_set_tuning(armon_ctx* ctx, const char* knob, int value)
     else if (!strcmp(knob, "ARMON_X_ROWS")) ctx->tune_x_rows = (value == 1 || value == 2) ? value : 0;
     else if (!strcmp(knob, "ARMON_Y_SX")) ctx->tune_y_sx = (value == 1 || value == 2) ? value : 0;
     else if (!strcmp(knob, "ARMON_COPY_NT")) ctx->tune_copy_nt = value & 3;
+    else if (!strcmp(knob, "PROFILE_WGS")) ctx->tune_profile_wgs = value > 0 ? value : 0;
     else ARMON_REQUIRE(false, "unknown tuning knob '%s'", knob);
     return ARMON_OK;
 }
@@ -136,6 +137,7 @@ int armon_hip_get_tuning(armon_ctx* ctx, const char* knob, int* value)
     else if (!strcmp(knob, "ARMON_X_ROWS")) *value = ctx->tune_x_rows;
     else if (!strcmp(knob, "ARMON_Y_SX")) *value = ctx->tune_y_sx;
     else if (!strcmp(knob, "ARMON_COPY_NT")) *value = ctx->tune_copy_nt;
+    else if (!strcmp(knob, "PROFILE_WGS")) *value = ctx->tune_profile_wgs;
     else if (!strcmp(knob, "Y_RUN_ROWS")) *value = ctx->tune_y_seg > 0 ? ctx->tune_y_seg : ctx->seg_value;
     else ARMON_REQUIRE(false, "unknown tuning knob '%s'", knob);
     return ARMON_OK;

@@ -261,3 +261,40 @@ def step_checkpoint(params, grid, step_label, axis_letter):
         write_sub_domain_file(params, grid, name + "_diff", no_msg=True)
         print(f"Difference file written to {name}_diff")
     return different
+
+
+PROFILE_COLUMNS = ("coord", "n", "rho", "un", "ut", "E", "p", "rho_min", "rho_max", "p_min", "p_max")
+
+
+def write_profile_file(path, profile, precision=17):
+    """A profile (profile.Profile) as text: a header line — kind, centre and dr (r) or width (x, y), cycle, time — then one
+    line per bin: coordinate, n, the five means, the four extrema, at ``precision`` digits (17 reads back bit for bit)."""
+    t = profile.table()
+    fmt = _fmt(precision)
+    head = [f"# profile kind={t['kind']}"]
+    if t["kind"] == "r":
+        head += [f"centre_x={fmt % t['centre'][0]}", f"centre_y={fmt % t['centre'][1]}", f"dr={fmt % t['dr']}"]
+    else:
+        head.append(f"width={t['width']}")
+    head += [f"cycle={t['cycle']}", f"time={fmt % t['time']}"]
+    with open(path, "w") as f:
+        f.write(" ".join(h.replace("= ", "=") for h in head) + "\n")
+        f.write("# " + ", ".join(PROFILE_COLUMNS) + "\n")
+        for b in range(len(t["n"])):
+            f.write(", ".join(str(int(t[c][b])) if c == "n" else fmt % t[c][b] for c in PROFILE_COLUMNS) + "\n")
+
+
+def read_profile_file(path):
+    """→ the dict of ``Profile.table()``: kind, cycle, time, centre and dr or width, and one fp64 array per column (``n``: uint64)."""
+    with open(path) as f:
+        head = dict(item.split("=", 1) for item in f.readline().split()[2:])
+        f.readline()
+        rows = [[v.strip() for v in line.split(",")] for line in f if line.strip()]
+    t = {"kind": head["kind"], "cycle": int(head["cycle"]), "time": float(head["time"])}
+    if t["kind"] == "r":
+        t["centre"], t["dr"] = (float(head["centre_x"]), float(head["centre_y"])), float(head["dr"])
+    else:
+        t["width"] = int(head["width"])
+    for k, c in enumerate(PROFILE_COLUMNS):
+        t[c] = np.array([int(r[k]) for r in rows], dtype=np.uint64) if c == "n" else np.array([float(r[k]) for r in rows], dtype=np.float64)
+    return t

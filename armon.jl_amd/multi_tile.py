@@ -310,6 +310,7 @@ class TileGroup(NativeGroup):
         saved_at, save_ns = -1, 0         # checkpoints are disk I/O: their time is taken out of the solve time
         compared_at, stopped = -1, False  # (and so is the time of the comparisons with a reference run's checkpoints)
         self.state_diffs = []
+        profiled_at, self.profiles = -1, []   # (and the time of the profiles)
         while gdt.time < maxtime and gdt.cycle < p0.maxcycle:
             self.solver_cycle(last_cycle=S.cycle_ends(p0, gdt))
             gdt.next_cycle()
@@ -319,6 +320,13 @@ class TileGroup(NativeGroup):
                 self.save_state(checkpoint_path(p0, gdt.cycle))
                 save_ns += _time.perf_counter_ns() - t_save
                 saved_at = gdt.cycle
+            if p0.profile_step != 0 and gdt.cycle % p0.profile_step == 0:
+                from .profile import profile_run
+                self.wait()
+                t_save = _time.perf_counter_ns()
+                profile_run(self, p0, gdt)
+                save_ns += _time.perf_counter_ns() - t_save
+                profiled_at = gdt.cycle
             if p0.compare_step != 0 and gdt.cycle % p0.compare_step == 0:
                 from .compare import compare_run
                 self.wait()
@@ -333,6 +341,9 @@ class TileGroup(NativeGroup):
         solve_ns = _time.perf_counter_ns() - t1 - save_ns
         if p0.checkpoint_at_end and saved_at != gdt.cycle:
             self.save_state(checkpoint_path(p0, gdt.cycle))
+        if p0.profile_at_end and profiled_at != gdt.cycle:
+            from .profile import profile_run
+            profile_run(self, p0, gdt)
         if p0.compare_at_end and compared_at != gdt.cycle and not stopped:
             from .compare import compare_run
             compare_run(self, p0, gdt)
@@ -345,7 +356,8 @@ class TileGroup(NativeGroup):
         gdt, g = self.global_dt, self.root.global_grid
         cells = g[0] * g[1]
         return S.SolverStats(float(gdt.time), float(gdt.current_dt), gdt.cycle, solve_ns / 1e9, cells,
-                             gdt.cycle * cells / max(solve_ns, 1), data=self, state_diffs=list(self.state_diffs))
+                             gdt.cycle * cells / max(solve_ns, 1), data=self, state_diffs=list(self.state_diffs),
+                             profiles=list(self.profiles))
 
     # ---- checkpoint / restart (checkpoint.py) ---------------------------------------------------------------------
     def _tiles_at_rest(self):
@@ -373,6 +385,12 @@ class TileGroup(NativeGroup):
         """``BlockGrid.compare_state`` of the whole domain: the merge of the tiles' records = the single block's."""
         from . import compare
         return compare.compare_state(self._tiles_at_rest(), ref, rtol=rtol, atol=atol, names=names, limit=limit, band_rows=band_rows)
+
+    def profile(self, kind, bins=None, width=1, centre=None, dr=None, with_p=True, scale_exp=None):
+        """``BlockGrid.profile`` of the whole domain: the merge of the tiles' records = the single block's, word for word."""
+        from . import profile
+        return profile.profile_state(self._tiles_at_rest(), kind, bins=bins, width=width, centre=centre, dr=dr, with_p=with_p,
+                                     scale_exp=scale_exp)
 
     def gather(self, names=("rho", "u", "v", "E", "p")):
         """The real cells of every tile assembled into global (NY, NX) arrays on the host."""

@@ -218,7 +218,9 @@ class ArmonParameters:
                      compare=False, is_ref=False, comparison_tolerance=1e-10, check_result=False,
                      return_data=False, checkpoint_step=0, checkpoint_file="checkpoint", checkpoint_at_end=False,
                      restart_from=None, compare_step=0, compare_dir=None, compare_file="checkpoint", compare_at_end=False,
-                     comparison_atol=0.0, comparison_time_atol=0.0, **options):
+                     comparison_atol=0.0, comparison_time_atol=0.0, profile_step=0, profile_kind="x", profile_bins=None,
+                     profile_width=1, profile_centre=None, profile_dr=None, profile_file="profile", profile_at_end=False,
+                     **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
         ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart).
@@ -227,7 +229,11 @@ class ArmonParameters:
         (relative) and ``comparison_atol`` (a number, or a dict plane → number); the file's time is compared with the run's
         within ``comparison_tolerance`` and ``comparison_time_atol``; ``compare_at_end``: with the file of the final cycle;
         the first difference is reported and stops the run (compare.py; the text ``compare`` / ``is_ref`` path is untouched by
-        these)."""
+        these).
+        ``profile_step=k``: after every k completed cycles (0 = off) the exact profile of the state (profile.py) along
+        ``profile_kind`` = ``"x" | "y" | "r"`` is written to ``<output_dir>/<profile_file>_<cycle:06d>.txt``;
+        ``profile_bins``, ``profile_width``, ``profile_centre``, ``profile_dr``: the arguments of ``profile.profile_state``
+        (None = its defaults); ``profile_at_end``: one when the run stops."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
         if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
             solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
@@ -270,6 +276,34 @@ class ArmonParameters:
                                    "one block or an in-process tile group only")
         if self.state_compare and self.compare_dir is None:
             solver_error("config", "compare_step / compare_at_end need compare_dir: the directory of the reference run's checkpoints")
+        if isinstance(profile_step, bool) or not isinstance(profile_step, (numbers.Integral, np.integer)) or profile_step < 0:
+            solver_error("config", f"profile_step must be an integer >= 0, got {profile_step!r}")
+        self.profile_step = int(profile_step)
+        self.profile_at_end = bool(profile_at_end)
+        self.profile_kind = str(profile_kind)
+        if self.profile_kind not in ("x", "y", "r"):
+            solver_error("config", f"unknown profile_kind {profile_kind!r}: 'x', 'y' or 'r'")
+        if isinstance(profile_width, bool) or not isinstance(profile_width, (numbers.Integral, np.integer)) or profile_width < 1:
+            solver_error("config", f"profile_width must be an integer >= 1, got {profile_width!r}")
+        self.profile_width = int(profile_width)
+        if profile_bins is not None and (isinstance(profile_bins, bool) or not isinstance(profile_bins, (numbers.Integral, np.integer))
+                                         or profile_bins < 1):
+            solver_error("config", f"profile_bins must be an integer >= 1, got {profile_bins!r}")
+        self.profile_bins = None if profile_bins is None else int(profile_bins)
+        if profile_dr is not None and (isinstance(profile_dr, bool) or not isinstance(profile_dr, (numbers.Real, np.floating))
+                                       or not (0 < profile_dr < float("inf"))):
+            solver_error("config", f"profile_dr must be a finite number > 0, got {profile_dr!r}")
+        self.profile_dr = None if profile_dr is None else float(profile_dr)
+        if profile_centre is not None and (len(profile_centre) != 2 or not all(np.isfinite(float(c)) for c in profile_centre)):
+            solver_error("config", f"profile_centre takes two finite coordinates, got {profile_centre!r}")
+        self.profile_centre = None if profile_centre is None else tuple(float(c) for c in profile_centre)
+        self.profile_file = str(profile_file)
+        if not self.profile_file or "/" in self.profile_file:
+            solver_error("config", f"profile_file is a file name inside output_dir, got {profile_file!r}")
+        self.state_profile = self.profile_step != 0 or self.profile_at_end      # any profile taken during the run
+        if self.state_profile and self.use_MPI:
+            solver_error("config", "profile_step / profile_at_end are not supported for ranks of a process group (use_MPI=true): "
+                                   "one block or an in-process tile group only")
         self.silent = silent
         self.output_dir, self.output_file = output_dir, output_file
         self.write_output, self.write_ghosts = write_output, write_ghosts

@@ -36,6 +36,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     timer: object = None
     grid_log: object = None
     state_diffs: list = field(default_factory=list)     # (cycle, compare.StateDiff) of compare_step / compare_at_end
+    profiles: list = field(default_factory=list)        # (cycle, profile.Profile) of profile_step / profile_at_end
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -165,6 +166,7 @@ class BlockGrid:
         self.halo_prefetch = None              # (axis, handle) of an exchange posted ahead of its sweep
         self._coarse_xy = {}                   # (fx, fy) -> coordinates of the coarse cells (coarse_coordinates)
         self.state_diffs = []                  # (cycle, StateDiff) of the run's compare_step / compare_at_end
+        self.profiles = []                     # (cycle, Profile) of the run's profile_step / profile_at_end
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -394,6 +396,14 @@ class BlockGrid:
         global grid and data type — computed on the device (compare.py) → ``compare.StateDiff``."""
         from . import compare
         return compare.compare_state([(self.params, self)], ref, rtol=rtol, atol=atol, names=names, limit=limit, band_rows=band_rows)
+
+    def profile(self, kind, bins=None, width=1, centre=None, dr=None, with_p=True, scale_exp=None):
+        """The exact 1-D profile of this block's state along ``kind`` = ``"x" | "y" | "r"``, computed on the device
+        (profile.py states the rule and the arguments) → ``profile.Profile``."""
+        from . import profile
+        self.params.wait()
+        return profile.profile_state([(self.params, self)], kind, bins=bins, width=width, centre=centre, dr=dr, with_p=with_p,
+                                     scale_exp=scale_exp)
 
     def real_view(self, a):
         g = self.size.ghosts
@@ -943,6 +953,8 @@ def graph_cycles_usable(params):
         return False                    # checkpoints are written, and a restart is primed, between host-driven cycles
     if params.state_compare or params.compare_dir is not None:
         return False                    # and so is a state compared with a reference run's checkpoint
+    if params.state_profile:
+        return False                    # and a profile taken
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
@@ -1142,6 +1154,7 @@ def time_loop(params, grid):
     saved_at, save_ns = -1, 0             # checkpoints are disk I/O: their time is taken out of the solve time
     compared_at, stopped = -1, False      # (and so is the time of the comparisons with a reference run's checkpoints)
     grid.state_diffs = []
+    profiled_at, grid.profiles = -1, []   # (and the time of the profiles)
     while gdt.time < maxtime and gdt.cycle < params.maxcycle:
         ends = cycle_ends(params, gdt)
         # animation frames (ref :373-378) are written after next_cycle! when (cycle - 1) % animation_step == 0; the fused
@@ -1169,6 +1182,13 @@ def time_loop(params, grid):
             grid.save_state(checkpoint_path(params, gdt.cycle))
             save_ns += _time.perf_counter_ns() - t_save
             saved_at = gdt.cycle
+        if params.profile_step != 0 and gdt.cycle % params.profile_step == 0:
+            from .profile import profile_run
+            params.wait()
+            t_save = _time.perf_counter_ns()
+            profile_run(grid, params, gdt)
+            save_ns += _time.perf_counter_ns() - t_save
+            profiled_at = gdt.cycle
         if params.compare_step != 0 and gdt.cycle % params.compare_step == 0:
             from .compare import compare_run
             params.wait()
@@ -1184,6 +1204,9 @@ def time_loop(params, grid):
     if params.checkpoint_at_end and saved_at != gdt.cycle:
         from .checkpoint import checkpoint_path
         grid.save_state(checkpoint_path(params, gdt.cycle))
+    if params.profile_at_end and profiled_at != gdt.cycle:
+        from .profile import profile_run
+        profile_run(grid, params, gdt)
     if params.compare_at_end and compared_at != gdt.cycle and not stopped:
         from .compare import compare_run
         compare_run(grid, params, gdt)
@@ -1220,6 +1243,7 @@ def armon(params):
         write_slices_files(params, grid, params.output_file)
     stats = SolverStats(final_time, dt, cycles, solve_time / 1e9, params.N[0] * params.N[1], cells_per_ns)
     stats.state_diffs = list(grid.state_diffs)
+    stats.profiles = list(grid.profiles)
     if params.return_data:
         stats.data = grid
     return stats

@@ -100,7 +100,8 @@ ARMON_API void* armon_hip_stream(armon_ctx* ctx);                              /
  * 4 rows, 2 = 4 consecutive strips of one row, 0 = automatic (the former for fp64, the latter for fp32),
  * "ARMON_Y_SX" store exchange of the Y march (rows stored in sector-aligned windows handed over through LDS): 1 = always,
  * 2 = never, 0 = automatic (when the row pitch is not a multiple of a 64-B sector), "ARMON_COPY_NT" the measurement aid
- * armon_hip_stream_copy4 with non-temporal loads (bit 0) / stores (bit 1).
+ * armon_hip_stream_copy4 with non-temporal loads (bit 0) / stores (bit 1), "PROFILE_WGS" cap on the workgroups of
+ * armon_hip_profile / armon_hip_profile_bounds, 0 = automatic (not read from the environment).
  * None of them changes a result bit. */
 ARMON_API int armon_hip_set_tuning(armon_ctx* ctx, const char* knob, int value);
 /* the current value of a knob; and, read-only, "Y_RUN_ROWS": rows per run the last automatic choice of the Y march took (0
@@ -316,6 +317,67 @@ ARMON_API int armon_hip_state_compare_f32(armon_ctx*, int64_t row_length, int ng
         const float* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
         int64_t global_nx, const float* ref_dense_dev, double rtol, double atol, armon_state_diff* diff_dev,
         uint32_t* row_out_dev);
+
+/* ---- in-situ profiles: exact binned sums along x, y or a radius (no reference counterpart; csrc/profile.hip) ---- */
+enum { ARMON_PROFILE_X = 0, ARMON_PROFILE_Y = 1, ARMON_PROFILE_R = 2 };
+/* One bin: 24 words = 192 B; every field merges by an associative, commutative integer operation, so the record of a domain
+ * is the merge of the records of its parts, word for word, whatever the split, the launch shape, the alignment or the ghost
+ * width. A sum is kept as three signed limbs: its value is (sum[k][0] + sum[k][1] 2^32 + sum[k][2] 2^64) 2^s_k. Every cell
+ * adds limbs below 2^32, so NO LIMB CAN OVERFLOW WHILE FEWER THAN 2^31 CELLS ARE MERGED INTO ONE BIN (a 32768^2 grid has 2^30
+ * cells); beyond that the words wrap silently. The order keys are key(x) = bits ^ (sign ? ~0 : 1 << 63) of the fp64 value:
+ * their unsigned order is the numerical order, with -0.0 below +0.0. */
+typedef struct {
+    uint64_t n;             /* cells added                                              (sum) */
+    uint64_t n_bad;         /* cells refused, see armon_hip_profile                     (sum) */
+    int64_t  sum[5][3];     /* rho, rho*un, rho*ut, rho*E, p: three signed limbs each   (sum, limb by limb, no carry) */
+    uint64_t rho_min, rho_max, p_min, p_max;   /* order keys                            (min / max) */
+    uint64_t reserved[3];   /* zero */
+} armon_profile_bin;
+typedef struct {
+    int32_t kind, eos;      /* ARMON_PROFILE_*; ARMON_EOS_* or -1 = no p (sum[4], p_min, p_max stay neutral) */
+    int64_t nbins, width;   /* width: cells per bin, X and Y */
+    double  cx, cy, dx, dy, inv_dr;   /* R: centre in cell units of the GLOBAL grid (cell gx covers [gx, gx+1)), cell sizes, 1/dr */
+    double  gamma;
+    int32_t scale_exp[5];   /* s_k: quantum of sum k is 2^s_k, -4096 <= s_k <= 4096 */
+} armon_profile_spec;
+
+/* Write the neutral element of the merge into bins_dev[0 .. nbins): zeros, the min keys all ones, the max keys zero. Async. */
+ARMON_API int armon_hip_profile_reset(armon_ctx*, int64_t nbins, armon_profile_bin* bins_dev);
+
+/* MERGE the real cells [col0, col0 + wnx) x [row0, row0 + wny) of one block into bins_dev[0 .. nbins). Block, window and
+ * their checks are those of armon_hip_state_pack; (global_col0, global_row0) >= 0 is the global 0-based position of the
+ * window's first cell. Also refused (ARMON_ERR_INVALID_ARG, nothing written): a NULL pointer, nbins < 1, width < 1, an unknown
+ * kind or eos, a scale_exp outside [-4096, 4096], and for R a dx, dy or inv_dr that is not finite and > 0 or a centre that is
+ * not finite. `spec` is HOST memory, read before the call returns.
+ * Per cell at the global position (gx, gy), all arithmetic in fp64 whatever the data type (fp32 values are converted
+ * first), one IEEE operation per operation written, correctly rounded division and square root:
+ *   bin    X: b = gx / width.  Y: b = gy / width.  R: rx = ((double)gx + 0.5 - cx) dx, ry likewise,
+ *          rr = sqrt(rx rx + ry ry), b = floor(rr inv_dr). A cell with b >= nbins is skipped and counted nowhere.
+ *   un, ut X: u, v.  Y: v, u.  R: (u rx + v ry) / rr and (v rx - u ry) / rr, both 0 when rr == 0.
+ *   terms  t0 = rho, t1 = rho un, t2 = rho ut, t3 = rho E, t4 = p: the EOS of this cell's (rho, E, u, v) evaluated IN THE DATA
+ *          TYPE with the operations of the EOS kernels, then converted to fp64. No p vector is read.
+ *   Q_k    = round-half-even(t_k / 2^s_k), an exact integer.
+ *   bad    any of rho, u, v, E or a t_k not finite, or a |Q_k| >= 2^95: the cell adds 1 to n_bad and nothing else.
+ *   limbs  with a = |Q_k|: a & 0xffffffff, (a >> 32) & 0xffffffff, a >> 64, each negated when Q_k < 0, each added to its own
+ *          int64. rho and p enter rho_min .. p_max through their order keys.
+ * No ghost cell is read. Integer atomics only (order-independent: the words are a function of the state, the spec and the
+ * scale), no scratch, async on the context's stream with no host synchronisation. The tuning knob PROFILE_WGS
+ * (armon_hip_set_tuning; 0 = automatic) caps the number of workgroups and changes no result bit. */
+ARMON_API int armon_hip_profile(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        const double* rho, const double* u, const double* v, const double* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_profile_spec* spec, armon_profile_bin* bins_dev);
+ARMON_API int armon_hip_profile_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        const float* rho, const float* u, const float* v, const float* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_profile_spec* spec, armon_profile_bin* bins_dev);
+
+/* Same geometry, spec and checks (scale_exp is not used): bounds_dev[k] = max(bounds_dev[k], bit pattern of the largest FINITE
+ * |t_k| of the window's cells), as unsigned integers; cells past the last bin count too. The default scale comes from this. */
+ARMON_API int armon_hip_profile_bounds(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        const double* rho, const double* u, const double* v, const double* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_profile_spec* spec, uint64_t bounds_dev[5]);
+ARMON_API int armon_hip_profile_bounds_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        const float* rho, const float* u, const float* v, const float* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_profile_spec* spec, uint64_t bounds_dev[5]);
 
 /* ---- fp32 variants (ref data_type=Float32, src/parameters.jl:185): same kernels, float arrays and scalars ---- */
 typedef struct {
