@@ -88,6 +88,22 @@ class ProfileSpec(C.Structure):
                 ("gamma", C.c_double), ("scale_exp", C.c_int32 * 5)]
 
 
+class ExactSpec(C.Structure):
+    """armon_exact_spec — an exact solution: a Riemann problem or a 1-D table along x, y or a radius (include/armon_hip.h)."""
+    _fields_ = [("form", C.c_int32), ("coord", C.c_int32), ("samples", C.c_int32), ("eos", C.c_int32), ("global_nx", C.c_int64),
+                ("cx", C.c_double), ("cy", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("gamma", C.c_double),
+                ("coord_min", C.c_double), ("coord_max", C.c_double), ("scale_exp", (C.c_int32 * 2) * 4),
+                ("time", C.c_double), ("side", (C.c_double * 4) * 2), ("star", C.c_double * 4), ("speed", C.c_double * 5),
+                ("g1", C.c_double), ("g2", C.c_double * 2), ("g3", C.c_double),
+                ("inv_scale", C.c_double), ("M", C.c_int64), ("outer", C.c_double * 3), ("table", C.c_void_p)]
+
+
+class ExactNorm(C.Structure):
+    """armon_exact_norm — one variable's distance from an exact solution, 16 words (include/armon_hip.h)."""
+    _fields_ = [("n", C.c_uint64), ("n_bad", C.c_uint64), ("sum_d", C.c_int64 * 3), ("sum_abs", C.c_int64 * 3),
+                ("sum_sq", C.c_int64 * 3), ("max_abs", C.c_uint64), ("max_abs_at", C.c_uint64), ("reserved", C.c_uint64 * 3)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -165,6 +181,9 @@ SIGNATURES = {
     "armon_hip_profile_reset": (_ci, [_vp, _i64, _dp]),
     "armon_hip_profile": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ProfileSpec), _dp]),
     "armon_hip_profile_bounds": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ProfileSpec), _dp]),
+    "armon_hip_exact_norms_reset": (_ci, [_vp, _dp]),
+    "armon_hip_exact_norms": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ExactSpec), _dp]),
+    "armon_hip_exact_fill": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ExactSpec)]),
     "armon_hip_sweep": (_ci, [_vp, C.POINTER(SweepDesc)]),
     "armon_hip_dt_state_step": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
     "armon_hip_dt_state_step_f32": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
@@ -232,6 +251,8 @@ def _add_f32_signatures():
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
     SIGNATURES["armon_hip_profile_f32"] = SIGNATURES["armon_hip_profile"]
     SIGNATURES["armon_hip_profile_bounds_f32"] = SIGNATURES["armon_hip_profile_bounds"]
+    SIGNATURES["armon_hip_exact_norms_f32"] = SIGNATURES["armon_hip_exact_norms"]
+    SIGNATURES["armon_hip_exact_fill_f32"] = SIGNATURES["armon_hip_exact_fill"]
     SIGNATURES["armon_hip_tune_placement_f32"] = SIGNATURES["armon_hip_tune_placement"]
     SIGNATURES["armon_hip_choose_placement_f32"] = SIGNATURES["armon_hip_choose_placement"]
 

@@ -1,0 +1,75 @@
+// exact_sum.hpp — the fixed-point addends of the decomposition-independent sums (profile.hip, analytic.hip) and the lane loads
+// both passes share. A term t is rounded ONCE, on its own, to Q = round-half-even(t / 2^s); |Q| is cut into three limbs below
+// 2^32, each negated when Q < 0 and each added to its own int64. Everything after the rounding is integer addition, so a
+// sum is a function of its addends only, word for word.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace armon {
+namespace exact {
+
+typedef unsigned long long u64;
+typedef unsigned __int128 u128;
+
+template <typename T> struct wide;
+template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
+template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
+
+__device__ __forceinline__ u64 bits_of(double v) { return (u64)__double_as_longlong(v); }
+__device__ __forceinline__ bool finite(double v) { return (bits_of(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
+
+// V cells of a row from `src`: one 16-B non-temporal load when WIDE and the lane has all V of them, element loads otherwise
+template <typename T, bool WIDE>
+__device__ __forceinline__ void load_cells(const T* __restrict__ src, bool whole, int64_t left, T f[wide<T>::n])
+{
+    constexpr int V = wide<T>::n;
+    typedef typename wide<T>::type VT;
+    if (WIDE && whole) {
+        const VT w = __builtin_nontemporal_load(reinterpret_cast<const VT*>(src));
+#pragma unroll
+        for (int c = 0; c < V; c++) f[c] = w[c];
+    } else {
+#pragma unroll
+        for (int c = 0; c < V; c++) f[c] = c < left ? __builtin_nontemporal_load(src + c) : T(0.);
+    }
+}
+
+// Q = round-half-even(t / 2^s) → a = |Q|; false when t is not finite or |Q| >= 2^95
+__device__ __forceinline__ bool quantise(double t, int s, u128& a)
+{
+    const u64 b = bits_of(t), frac = b & ((1ull << 52) - 1);
+    const int ef = (int)((b >> 52) & 0x7ff);
+    a = 0;
+    if (ef == 0x7ff) return false;
+    const u64 m = ef ? (frac | (1ull << 52)) : frac;                // t = ±m 2^e
+    if (m == 0) return true;
+    const int64_t sh = (int64_t)(ef ? ef : 1) - 1075 - (int64_t)s;
+    if (sh >= 0) {
+        if (sh >= 95) return false;
+        const int room = 95 - (int)sh;                              // m << sh < 2^95  <=>  m < 2^room
+        if (room < 64 && (m >> room) != 0) return false;
+        a = (u128)m << (int)sh;
+    } else if (sh > -64) {
+        const int r = (int)-sh;
+        const u64 rem = m & ((1ull << r) - 1), half = 1ull << (r - 1);
+        u64 q = m >> r;
+        q += (rem > half) || (rem == half && (q & 1));
+        a = q;                                                      // <= 2^52: never near the edge
+    }                                                               // (m < 2^53: a shift by 64 or more rounds to 0)
+    return true;
+}
+
+// the three limbs of a = |Q| into their sums, negated when the term is negative
+__device__ __forceinline__ void add_limbs(long long sum[3], u128 a, bool neg)
+{
+    const long long l0 = (long long)((u64)a & 0xffffffffull), l1 = (long long)((u64)a >> 32), l2 = (long long)(u64)(a >> 64);
+    sum[0] += neg ? -l0 : l0;
+    sum[1] += neg ? -l1 : l1;
+    sum[2] += neg ? -l2 : l2;
+}
+
+}  // namespace exact
+}  // namespace armon

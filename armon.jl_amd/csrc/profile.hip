@@ -41,6 +41,7 @@
 // reports for the variant launched. Equal-bin neighbours of R are not combined across lanes before the LDS: a record is 21
 // words, and the ds atomics of lanes in different bins do not serialise.
 #include "common.hpp"
+#include "exact_sum.hpp"
 #include "reduce.hpp"
 
 #include <cmath>
@@ -58,17 +59,16 @@ constexpr int kTable = 264;                 // bins of the LDS table: a span is 
                                             // and R over square cells at dr = dx reaches 133 or 261
 constexpr int W_N = 0, W_BAD = 1, W_SUM = 2, W_RHO_MIN = 17, W_RHO_MAX = 18, W_P_MIN = 19, W_P_MAX = 20;
 
-typedef unsigned long long u64;
-typedef unsigned __int128 u128;
+using exact::u64;
+using exact::u128;
+using exact::wide;
+using exact::bits_of;
+using exact::finite;
+using exact::load_cells;
+using exact::quantise;
 
 static_assert(sizeof(armon_profile_bin) == kRecWords * 8, "armon_profile_bin is 24 words");
 
-template <typename T> struct wide;
-template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ u64 bits_of(double v) { return (u64)__double_as_longlong(v); }
-__device__ __forceinline__ bool finite(double v) { return (bits_of(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 __device__ __forceinline__ u64 order_key(double v) { const u64 b = bits_of(v); return b ^ ((b >> 63) ? ~0ull : (1ull << 63)); }
 __device__ __forceinline__ bool is_min_word(int w) { return w == W_RHO_MIN || w == W_P_MIN; }
 __device__ __forceinline__ bool is_max_word(int w) { return w == W_RHO_MAX || w == W_P_MAX; }
@@ -85,46 +85,6 @@ struct prof_args {
     u64* bins;                      // [nbins][kRecWords]
     u64* bounds;                    // [5] (the bounds pass)
 };
-
-template <typename T, bool WIDE>
-__device__ __forceinline__ void load_cells(const T* __restrict__ src, bool whole, int64_t left, T f[wide<T>::n])
-{
-    constexpr int V = wide<T>::n;
-    typedef typename wide<T>::type VT;
-    if (WIDE && whole) {
-        const VT w = __builtin_nontemporal_load(reinterpret_cast<const VT*>(src));
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = w[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = c < left ? __builtin_nontemporal_load(src + c) : T(0.);
-    }
-}
-
-// Q = round-half-even(t / 2^s) → a = |Q|; false when t is not finite or |Q| >= 2^95
-__device__ __forceinline__ bool quantise(double t, int s, u128& a)
-{
-    const u64 b = bits_of(t), frac = b & ((1ull << 52) - 1);
-    const int ef = (int)((b >> 52) & 0x7ff);
-    a = 0;
-    if (ef == 0x7ff) return false;
-    const u64 m = ef ? (frac | (1ull << 52)) : frac;                // t = ±m 2^e
-    if (m == 0) return true;
-    const int64_t sh = (int64_t)(ef ? ef : 1) - 1075 - (int64_t)s;
-    if (sh >= 0) {
-        if (sh >= 95) return false;
-        const int room = 95 - (int)sh;                              // m << sh < 2^95  <=>  m < 2^room
-        if (room < 64 && (m >> room) != 0) return false;
-        a = (u128)m << (int)sh;
-    } else if (sh > -64) {
-        const int r = (int)-sh;
-        const u64 rem = m & ((1ull << r) - 1), half = 1ull << (r - 1);
-        u64 q = m >> r;
-        q += (rem > half) || (rem == half && (q & 1));
-        a = q;                                                      // <= 2^52: never near the edge
-    }                                                               // (m < 2^53: a shift by 64 or more rounds to 0)
-    return true;
-}
 
 struct lane_rec {
     u64 n, n_bad;
@@ -199,11 +159,7 @@ __device__ __forceinline__ void add_cell(const armon_profile_spec& s, T rho, T u
     acc.n += 1;
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-        const long long l0 = (long long)((u64)a[k] & 0xffffffffull), l1 = (long long)((u64)a[k] >> 32), l2 = (long long)(u64)(a[k] >> 64);
-        const bool neg = bits_of(t[k]) >> 63;
-        acc.sum[k][0] += neg ? -l0 : l0;
-        acc.sum[k][1] += neg ? -l1 : l1;
-        acc.sum[k][2] += neg ? -l2 : l2;
+        exact::add_limbs(acc.sum[k], a[k], bits_of(t[k]) >> 63);
     }
     const u64 kr = order_key(t[0]);
     acc.rho_min = kr < acc.rho_min ? kr : acc.rho_min;

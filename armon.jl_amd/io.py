@@ -298,3 +298,35 @@ def read_profile_file(path):
     for k, c in enumerate(PROFILE_COLUMNS):
         t[c] = np.array([int(r[k]) for r in rows], dtype=np.uint64) if c == "n" else np.array([float(r[k]) for r in rows], dtype=np.float64)
     return t
+
+
+ERROR_NORMS_COLUMNS = ("l1", "l2", "linf", "bias")
+
+
+def write_error_norms_file(path, norms, precision=17):
+    """Error norms (analytic.ErrorNorms) as text: a header line — cycle, time, samples, n, n_bad — then one line per variable
+    (rho, un, ut, p): L1, L2, Linf, bias at ``precision`` digits (17 reads back bit for bit) and the global cell (gx, gy) that
+    attains Linf, -1 -1 when no cell differs."""
+    t = norms.table()
+    fmt = _fmt(precision)
+    with open(path, "w") as f:
+        f.write(f"# error_norms cycle={t['cycle']} time={(fmt % t['time']).strip()} samples={t['samples']} n={t['n']} n_bad={t['n_bad']}\n")
+        f.write("# variable, " + ", ".join(ERROR_NORMS_COLUMNS) + ", linf_gx, linf_gy\n")
+        for name in ("rho", "un", "ut", "p"):
+            at = t[name]["linf_at"] or (-1, -1)
+            f.write(", ".join([name] + [fmt % t[name][c] for c in ERROR_NORMS_COLUMNS] + [str(at[0]), str(at[1])]) + "\n")
+
+
+def read_error_norms_file(path):
+    """→ the dict of ``ErrorNorms.table()``."""
+    with open(path) as f:
+        head = dict(item.split("=", 1) for item in f.readline().split()[2:])
+        f.readline()
+        rows = [[v.strip() for v in line.split(",")] for line in f if line.strip()]
+    t = {"cycle": int(head["cycle"]), "time": float(head["time"]), "samples": int(head["samples"]), "n": int(head["n"]),
+         "n_bad": int(head["n_bad"])}
+    for r in rows:
+        at = (int(r[5]), int(r[6]))
+        t[r[0]] = {c: float(r[1 + k]) for k, c in enumerate(ERROR_NORMS_COLUMNS)}
+        t[r[0]]["linf_at"] = None if at == (-1, -1) else at
+    return t

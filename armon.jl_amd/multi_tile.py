@@ -304,6 +304,11 @@ class TileGroup(NativeGroup):
         self.dt_inflight.clear()
         if p0.restart_from is not None:
             self.load_state(p0.restart_from)
+        if p0.start_from_exact is not None:
+            self.fill_exact(time=p0.start_from_exact, samples=p0.error_norms_samples)
+            gdt.time = p0.T(p0.start_from_exact)     # the clock starts where the solution was taken
+            if p0.check_result or p0.silent <= 1:
+                p0.initial_mass, p0.initial_energy = self.conservation_vars()
         self.wait()
         t1 = _time.perf_counter_ns()
         maxtime = p0.T(p0.maxtime)
@@ -311,6 +316,7 @@ class TileGroup(NativeGroup):
         compared_at, stopped = -1, False  # (and so is the time of the comparisons with a reference run's checkpoints)
         self.state_diffs = []
         profiled_at, self.profiles = -1, []   # (and the time of the profiles)
+        normed_at, self.error_norms_taken = -1, []   # (and of the error norms)
         while gdt.time < maxtime and gdt.cycle < p0.maxcycle:
             self.solver_cycle(last_cycle=S.cycle_ends(p0, gdt))
             gdt.next_cycle()
@@ -327,6 +333,13 @@ class TileGroup(NativeGroup):
                 profile_run(self, p0, gdt)
                 save_ns += _time.perf_counter_ns() - t_save
                 profiled_at = gdt.cycle
+            if p0.error_norms_step != 0 and gdt.cycle % p0.error_norms_step == 0:
+                from .analytic import error_norms_run
+                self.wait()
+                t_save = _time.perf_counter_ns()
+                error_norms_run(self, p0, gdt)
+                save_ns += _time.perf_counter_ns() - t_save
+                normed_at = gdt.cycle
             if p0.compare_step != 0 and gdt.cycle % p0.compare_step == 0:
                 from .compare import compare_run
                 self.wait()
@@ -344,6 +357,9 @@ class TileGroup(NativeGroup):
         if p0.profile_at_end and profiled_at != gdt.cycle:
             from .profile import profile_run
             profile_run(self, p0, gdt)
+        if p0.error_norms_at_end and normed_at != gdt.cycle:
+            from .analytic import error_norms_run
+            error_norms_run(self, p0, gdt)
         if p0.compare_at_end and compared_at != gdt.cycle and not stopped:
             from .compare import compare_run
             compare_run(self, p0, gdt)
@@ -357,7 +373,7 @@ class TileGroup(NativeGroup):
         cells = g[0] * g[1]
         return S.SolverStats(float(gdt.time), float(gdt.current_dt), gdt.cycle, solve_ns / 1e9, cells,
                              gdt.cycle * cells / max(solve_ns, 1), data=self, state_diffs=list(self.state_diffs),
-                             profiles=list(self.profiles))
+                             profiles=list(self.profiles), error_norms=list(self.error_norms_taken))
 
     # ---- checkpoint / restart (checkpoint.py) ---------------------------------------------------------------------
     def _tiles_at_rest(self):
@@ -391,6 +407,21 @@ class TileGroup(NativeGroup):
         from . import profile
         return profile.profile_state(self._tiles_at_rest(), kind, bins=bins, width=width, centre=centre, dr=dr, with_p=with_p,
                                      scale_exp=scale_exp)
+
+    def error_norms(self, reference=None, time=None, samples=1, coord_range=None, window=None, scale_exp=None):
+        """``BlockGrid.error_norms`` of the whole domain: the merge of the tiles' records = the single block's, word for word.
+        ``window``: ``(col0, row0, wnx, wny)`` in real cells of the GLOBAL grid; each tile takes the part it holds."""
+        from . import analytic
+        tiles = self._tiles_at_rest()
+        return analytic.error_norms_state(tiles, reference, time=time, samples=samples, coord_range=coord_range,
+                                          windows=None if window is None else analytic.tile_windows(tiles, window), scale_exp=scale_exp)
+
+    def fill_exact(self, reference=None, time=None, samples=1, coord_range=None, window=None):
+        """``BlockGrid.fill_exact`` of the whole domain: every tile fills its own real cells (of the global ``window``)."""
+        from . import analytic
+        tiles = self._tiles_at_rest()
+        return analytic.fill_state(tiles, reference, time=time, samples=samples, coord_range=coord_range,
+                                   windows=None if window is None else analytic.tile_windows(tiles, window))
 
     def gather(self, names=("rho", "u", "v", "E", "p")):
         """The real cells of every tile assembled into global (NY, NX) arrays on the host."""

@@ -220,7 +220,8 @@ class ArmonParameters:
                      restart_from=None, compare_step=0, compare_dir=None, compare_file="checkpoint", compare_at_end=False,
                      comparison_atol=0.0, comparison_time_atol=0.0, profile_step=0, profile_kind="x", profile_bins=None,
                      profile_width=1, profile_centre=None, profile_dr=None, profile_file="profile", profile_at_end=False,
-                     **options):
+                     error_norms_step=0, error_norms_at_end=False, error_norms_samples=1, error_norms_file="error_norms",
+                     start_from_exact=None, **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
         ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart).
@@ -233,7 +234,12 @@ class ArmonParameters:
         ``profile_step=k``: after every k completed cycles (0 = off) the exact profile of the state (profile.py) along
         ``profile_kind`` = ``"x" | "y" | "r"`` is written to ``<output_dir>/<profile_file>_<cycle:06d>.txt``;
         ``profile_bins``, ``profile_width``, ``profile_centre``, ``profile_dr``: the arguments of ``profile.profile_state``
-        (None = its defaults); ``profile_at_end``: one when the run stops."""
+        (None = its defaults); ``profile_at_end``: one when the run stops.
+        ``error_norms_step=k``: after every k completed cycles (0 = off) the state's distance from the exact solution of the
+        test case at the run's time (analytic.py) is written to ``<output_dir>/<error_norms_file>_<cycle:06d>.txt`` and listed
+        in ``SolverStats.error_norms``; ``error_norms_samples``: 1, 2 or 4 points per cell and axis for the cell means of the
+        solution; ``error_norms_at_end``: one when the run stops. ``start_from_exact=t0``: the state is filled with the exact
+        solution at ``t0 > 0`` and the clock starts there, so that a convergence study skips the start-up error of the jump."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
         if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
             solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
@@ -304,6 +310,35 @@ class ArmonParameters:
         if self.state_profile and self.use_MPI:
             solver_error("config", "profile_step / profile_at_end are not supported for ranks of a process group (use_MPI=true): "
                                    "one block or an in-process tile group only")
+        if isinstance(error_norms_step, bool) or not isinstance(error_norms_step, (numbers.Integral, np.integer)) or error_norms_step < 0:
+            solver_error("config", f"error_norms_step must be an integer >= 0, got {error_norms_step!r}")
+        self.error_norms_step = int(error_norms_step)
+        self.error_norms_at_end = bool(error_norms_at_end)
+        if isinstance(error_norms_samples, bool) or error_norms_samples not in (1, 2, 4):
+            solver_error("config", f"error_norms_samples must be 1, 2 or 4, got {error_norms_samples!r}")
+        self.error_norms_samples = int(error_norms_samples)
+        self.error_norms_file = str(error_norms_file)
+        if not self.error_norms_file or "/" in self.error_norms_file:
+            solver_error("config", f"error_norms_file is a file name inside output_dir, got {error_norms_file!r}")
+        if start_from_exact is not None and (isinstance(start_from_exact, bool) or not isinstance(start_from_exact, (numbers.Real, np.floating))
+                                             or not (0 < start_from_exact < float("inf"))):
+            solver_error("config", f"start_from_exact must be a finite time > 0, got {start_from_exact!r}")
+        self.start_from_exact = None if start_from_exact is None else float(start_from_exact)
+        self.state_error_norms = self.error_norms_step != 0 or self.error_norms_at_end     # any error norms taken during the run
+        self.exact_solution = self.state_error_norms or self.start_from_exact is not None
+        if self.exact_solution and self.use_MPI:
+            solver_error("config", "error_norms_step / error_norms_at_end / start_from_exact are not supported for ranks of a process "
+                                   "group (use_MPI=true): one block or an in-process tile group only")
+        if self.start_from_exact is not None and (self.compare or self.is_ref):
+            solver_error("config", "start_from_exact cannot be combined with compare / is_ref: the step files of a reference run "
+                                   "start from the initial state at cycle 0")
+        if self.start_from_exact is not None and self.restart_from is not None:
+            solver_error("config", "start_from_exact cannot be combined with restart_from: both set the initial state and the clock")
+        if self.exact_solution:
+            from .analytic import NO_CLOSED_FORM
+            if self.test.name in NO_CLOSED_FORM:
+                solver_error("config", f"error_norms_step / error_norms_at_end / start_from_exact need a test case with an exact "
+                                       f"solution: {self.test.name} has no closed form")
         self.silent = silent
         self.output_dir, self.output_file = output_dir, output_file
         self.write_output, self.write_ghosts = write_output, write_ghosts

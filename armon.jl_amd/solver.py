@@ -37,6 +37,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     grid_log: object = None
     state_diffs: list = field(default_factory=list)     # (cycle, compare.StateDiff) of compare_step / compare_at_end
     profiles: list = field(default_factory=list)        # (cycle, profile.Profile) of profile_step / profile_at_end
+    error_norms: list = field(default_factory=list)     # (cycle, time, analytic.ErrorNorms or None: no solution at that time) of error_norms_step / error_norms_at_end
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -167,6 +168,7 @@ class BlockGrid:
         self._coarse_xy = {}                   # (fx, fy) -> coordinates of the coarse cells (coarse_coordinates)
         self.state_diffs = []                  # (cycle, StateDiff) of the run's compare_step / compare_at_end
         self.profiles = []                     # (cycle, Profile) of the run's profile_step / profile_at_end
+        self.error_norms_taken = []            # (cycle, time, ErrorNorms) of the run's error_norms_step / error_norms_at_end
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -404,6 +406,21 @@ class BlockGrid:
         self.params.wait()
         return profile.profile_state([(self.params, self)], kind, bins=bins, width=width, centre=centre, dr=dr, with_p=with_p,
                                      scale_exp=scale_exp)
+
+    def error_norms(self, reference=None, time=None, samples=1, coord_range=None, window=None, scale_exp=None):
+        """The distance of this block's state from an exact solution, reduced on the device (analytic.py states the rule and the
+        arguments) → ``analytic.ErrorNorms``. ``reference=None``: the test case's own solution at ``time``."""
+        from . import analytic
+        self.params.wait()
+        return analytic.error_norms_state([(self.params, self)], reference, time=time, samples=samples, coord_range=coord_range,
+                                          windows=None if window is None else [tuple(window)], scale_exp=scale_exp)
+
+    def fill_exact(self, reference=None, time=None, samples=1, coord_range=None, window=None):
+        """Write an exact solution (default: the test case's at ``time``) into rho, u, v, E of this block's real cells."""
+        from . import analytic
+        self.params.wait()
+        return analytic.fill_state([(self.params, self)], reference, time=time, samples=samples, coord_range=coord_range,
+                                   windows=None if window is None else [tuple(window)])
 
     def real_view(self, a):
         g = self.size.ghosts
@@ -955,6 +972,8 @@ def graph_cycles_usable(params):
         return False                    # and so is a state compared with a reference run's checkpoint
     if params.state_profile:
         return False                    # and a profile taken
+    if params.exact_solution:
+        return False                    # and error norms taken, or a start from the exact solution
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
@@ -1148,6 +1167,11 @@ def time_loop(params, grid):
     gdt = grid.global_dt
     if params.restart_from is not None:
         grid.load_state(params.restart_from)
+    if params.start_from_exact is not None:
+        grid.fill_exact(time=params.start_from_exact, samples=params.error_norms_samples)
+        gdt.time = params.T(params.start_from_exact)     # the clock starts where the solution was taken
+        if params.check_result or params.silent <= 1:
+            params.initial_mass, params.initial_energy = conservation_vars(params, grid)
     params.wait()
     t1 = _time.perf_counter_ns()
     maxtime = params.T(params.maxtime)
@@ -1155,6 +1179,7 @@ def time_loop(params, grid):
     compared_at, stopped = -1, False      # (and so is the time of the comparisons with a reference run's checkpoints)
     grid.state_diffs = []
     profiled_at, grid.profiles = -1, []   # (and the time of the profiles)
+    normed_at, grid.error_norms_taken = -1, []   # (and of the error norms)
     while gdt.time < maxtime and gdt.cycle < params.maxcycle:
         ends = cycle_ends(params, gdt)
         # animation frames (ref :373-378) are written after next_cycle! when (cycle - 1) % animation_step == 0; the fused
@@ -1189,6 +1214,13 @@ def time_loop(params, grid):
             profile_run(grid, params, gdt)
             save_ns += _time.perf_counter_ns() - t_save
             profiled_at = gdt.cycle
+        if params.error_norms_step != 0 and gdt.cycle % params.error_norms_step == 0:
+            from .analytic import error_norms_run
+            params.wait()
+            t_save = _time.perf_counter_ns()
+            error_norms_run(grid, params, gdt)
+            save_ns += _time.perf_counter_ns() - t_save
+            normed_at = gdt.cycle
         if params.compare_step != 0 and gdt.cycle % params.compare_step == 0:
             from .compare import compare_run
             params.wait()
@@ -1207,6 +1239,9 @@ def time_loop(params, grid):
     if params.profile_at_end and profiled_at != gdt.cycle:
         from .profile import profile_run
         profile_run(grid, params, gdt)
+    if params.error_norms_at_end and normed_at != gdt.cycle:
+        from .analytic import error_norms_run
+        error_norms_run(grid, params, gdt)
     if params.compare_at_end and compared_at != gdt.cycle and not stopped:
         from .compare import compare_run
         compare_run(grid, params, gdt)
@@ -1244,6 +1279,7 @@ def armon(params):
     stats = SolverStats(final_time, dt, cycles, solve_time / 1e9, params.N[0] * params.N[1], cells_per_ns)
     stats.state_diffs = list(grid.state_diffs)
     stats.profiles = list(grid.profiles)
+    stats.error_norms = list(grid.error_norms_taken)
     if params.return_data:
         stats.data = grid
     return stats

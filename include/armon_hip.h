@@ -379,6 +379,98 @@ ARMON_API int armon_hip_profile_bounds_f32(armon_ctx*, int64_t row_length, int n
         const float* rho, const float* u, const float* v, const float* E, int64_t col0, int64_t row0, int64_t wnx,
         int64_t wny, int64_t global_col0, int64_t global_row0, const armon_profile_spec* spec, uint64_t bounds_dev[5]);
 
+/* ---- exact solutions: the state's distance from one, and the state filled with one (no reference counterpart;
+ * csrc/analytic.hip) ---- */
+enum { ARMON_EXACT_RIEMANN = 0, ARMON_EXACT_TABLE = 1 };
+/* What the exact solution is. HOST memory, read before the call returns; only `table` points to device memory.
+ * The coordinate of a point is q = x (coord = ARMON_PROFILE_X), y (Y) or the distance from the centre (R), with
+ * x = (((double)gx + o) - cx) dx for the point at the fraction o of cell gx, y likewise: (cx, cy) is where the coordinate
+ * is 0 (the jump of a Riemann problem, the centre of a blast), in cell units of the GLOBAL grid.
+ * RIEMANN (perfect gas, gamma = 7/5 only: the fans use the integer powers 5 = 2/(gamma-1) and 7 = 2 gamma/(gamma-1)):
+ *   xi = q / time, the region is the first of  xi < speed[0]: left state;  xi < speed[1]: left fan;  xi < speed[2]: left star
+ *   state;  xi < speed[3]: right star state;  xi < speed[4]: right fan;  otherwise the right state. In a fan of side K, with
+ *   sign = +1 (left) or -1 (right):  r = g1 + sign (g2[K] (u_K - xi)),  r2 = r r, r4 = r2 r2, r5 = r4 r, r7 = r5 r2,
+ *   rho = rho_K r5,  p = p_K r7,  un = g1 (((sign c_K) + g3 u_K) + xi),  where the caller has set g1 = 2/(gamma+1),
+ *   g2[K] = (gamma-1)/((gamma+1) c_K), g3 = (gamma-1)/2. A shock has speed[head] == speed[tail]: its fan is never chosen.
+ * TABLE: lam = q inv_scale; not (lam < 1): the outer state; otherwise s = lam M, j = floor(s) clamped to [0, M - 1],
+ *   f = s - j, value = t[j] + f (t[j+1] - t[j]) for each of the three rows rho, un, p of table[3][M + 1]. */
+typedef struct {
+    int32_t form, coord;        /* ARMON_EXACT_*; ARMON_PROFILE_X / Y / R */
+    int32_t samples, eos;       /* 1, 2 or 4 points per cell and axis; ARMON_EOS_PERFECT_GAS */
+    int64_t global_nx;          /* row length of the global grid: positions are g = gy * global_nx + gx */
+    double  cx, cy, dx, dy, gamma;
+    double  coord_min, coord_max;   /* a cell whose CENTRE coordinate lies outside [min, max) is skipped and counted nowhere */
+    int32_t scale_exp[4][2];    /* per variable rho, un, ut, p: the quanta 2^s of (d, |d|) and of d^2; -4096 <= s <= 4096 */
+    double  time;               /* RIEMANN, > 0 */
+    double  side[2][4];         /* RIEMANN: rho, u, p, c of the left and of the right state */
+    double  star[4];            /* RIEMANN: p*, u*, rho*L, rho*R */
+    double  speed[5];           /* RIEMANN: left head, left tail, contact, right tail, right head, in order */
+    double  g1, g2[2], g3;      /* RIEMANN: see above */
+    double  inv_scale;          /* TABLE */
+    int64_t M;                  /* TABLE: intervals, >= 1 */
+    double  outer[3];           /* TABLE: rho, un, p where lam >= 1 */
+    const double* table;        /* TABLE: DEVICE memory, [3][M + 1] fp64 */
+} armon_exact_spec;
+/* One variable's distance from the exact solution: 16 words = 128 B. Every field merges by integer addition or by the
+ * pair maximum of armon_state_diff, so the record of a domain is the merge of the records of its parts, word for word.
+ * Sums are three signed limbs as in armon_profile_bin: value = (s[0] + s[1] 2^32 + s[2] 2^64) 2^scale. */
+typedef struct {
+    uint64_t n;             /* cells added                                              (sum) */
+    uint64_t n_bad;         /* cells refused                                            (sum) */
+    int64_t  sum_d[3];      /* d = state - reference, quantum 2^scale_exp[k][0]         (sum, limb by limb) */
+    int64_t  sum_abs[3];    /* |d|, quantum 2^scale_exp[k][0] */
+    int64_t  sum_sq[3];     /* d d, quantum 2^scale_exp[k][1] */
+    uint64_t max_abs;       /* bit pattern of the largest |d|                           (pair max) */
+    uint64_t max_abs_at;    /* smallest g that attains it; UINT64_MAX while max_abs == 0 */
+    uint64_t reserved[3];   /* zero */
+} armon_exact_norm;
+
+/* Write the neutral element of the merge into out_dev[0 .. 4): zeros, max_abs_at = UINT64_MAX. Async. */
+ARMON_API int armon_hip_exact_norms_reset(armon_ctx*, armon_exact_norm* out_dev);
+
+/* MERGE the distance of the real cells [col0, col0 + wnx) x [row0, row0 + wny) of one block from the exact solution `spec`
+ * into out_dev[0 .. 4), one record for each of rho, un, ut, p. Block, window, (global_col0, global_row0) and their checks
+ * are those of armon_hip_profile. Also refused (ARMON_ERR_INVALID_ARG, nothing written): a NULL pointer, an unknown form or
+ * coord, samples not 1, 2 or 4, an eos other than the perfect gas, RIEMANN with gamma != 7/5 or time not finite and > 0,
+ * TABLE with M < 1, a NULL table or an inv_scale not finite and > 0, dx, dy not finite and > 0, a centre or a coord_min /
+ * coord_max that is NaN, global_nx < 1, a scale_exp outside [-4096, 4096].
+ * Per cell at (gx, gy), all arithmetic in fp64 unless said otherwise, one IEEE operation per operation written, correctly
+ * rounded division and square root:
+ *   centre   rx = (((double)gx + 0.5) - cx) dx, ry likewise, rr = sqrt(rx rx + ry ry); q = rx, ry or rr; the cell is skipped
+ *            unless coord_min <= q < coord_max.
+ *   samples  o_i = ((double)i + 0.5) / samples. X and Y: the points o_i along the coordinate, i = 0 .. samples-1. R: the
+ *            points (o_i, o_j), j outer. Each point's (rho, un, p) by the rule of armon_exact_spec, summed in that order
+ *            from 0.0, the sum times 1 / (number of points).
+ *   stored   the reference AS THE DATA TYPE HOLDS IT (exactly what armon_hip_exact_fill writes): u, v = (un, 0), (0, un)
+ *            or (un rx / rr, un ry / rr) (both 0 where rr == 0), E = p / ((gamma - 1) rho) + 0.5 (u u + v v), then rho, u,
+ *            v, E converted to the data type.
+ *   vars     of the state's (rho, u, v, E) and of the stored reference's alike: rho; un, ut = u, v (X), v, u (Y) or
+ *            (u rx + v ry) / rr, (v rx - u ry) / rr, both 0 where rr == 0 (R), of the values converted to fp64; p = the
+ *            EOS evaluated IN THE DATA TYPE with the operations of the EOS kernels, then converted. No p vector is read.
+ *   d_k      = the state's variable k - the reference's. So a state written by armon_hip_exact_fill has d_k == 0 in every
+ *            cell, and the reference's transverse velocity is exactly 0 for X and Y.
+ *   sums     Q = round-half-even(t / 2^s) of t = d_k, |d_k| (s = scale_exp[k][0]) and d_k d_k (s = scale_exp[k][1]), limbs
+ *            as in armon_hip_profile; max_abs takes the bit pattern of |d_k| with g = gy * global_nx + gx.
+ *   bad      any of the eight values, a variable of either side or a d_k d_k not finite, or a |Q| >= 2^95: the cell adds 1
+ *            to n_bad of all four records and nothing else.
+ * No ghost cell is read, no float atomics; writes out_dev and the context's reduction scratch (52 x 8 x CUs words at most),
+ * which grows as in armon_hip_state_pack. Async on the context's stream. */
+ARMON_API int armon_hip_exact_norms(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        const double* rho, const double* u, const double* v, const double* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_exact_spec* spec, armon_exact_norm* out_dev);
+ARMON_API int armon_hip_exact_norms_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        const float* rho, const float* u, const float* v, const float* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_exact_spec* spec, armon_exact_norm* out_dev);
+
+/* Same geometry, spec and checks (scale_exp is not used): write the stored reference into rho, u, v, E of the window's real
+ * cells whose centre coordinate lies in [coord_min, coord_max). Ghosts and every other vector are untouched. Async. */
+ARMON_API int armon_hip_exact_fill(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        double* rho, double* u, double* v, double* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_exact_spec* spec);
+ARMON_API int armon_hip_exact_fill_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny,
+        float* rho, float* u, float* v, float* E, int64_t col0, int64_t row0, int64_t wnx,
+        int64_t wny, int64_t global_col0, int64_t global_row0, const armon_exact_spec* spec);
+
 /* ---- fp32 variants (ref data_type=Float32, src/parameters.jl:185): same kernels, float arrays and scalars ---- */
 typedef struct {
     float *x, *y, *rho, *u, *v, *E, *p, *c, *g, *us, *ps, *work_1, *work_2, *work_3, *work_4, *mask;
