@@ -104,6 +104,18 @@ class ExactNorm(C.Structure):
                 ("sum_sq", C.c_int64 * 3), ("max_abs", C.c_uint64), ("max_abs_at", C.c_uint64), ("reserved", C.c_uint64 * 3)]
 
 
+class HistoryRecord(C.Structure):
+    """armon_history_record — one sample of the run history, 40 words (include/armon_hip.h, armon_hip_history_sample)."""
+    _fields_ = [("n", C.c_uint64), ("n_bad", C.c_uint64), ("sum", (C.c_int64 * 3) * 6), ("ext", (C.c_uint64 * 2) * 8),
+                ("reserved", C.c_uint64 * 4)]
+
+
+class HistorySpec(C.Structure):
+    """armon_history_spec — the EOS, the global row length and the quanta of a history sample."""
+    _fields_ = [("eos", C.c_int32), ("reserved", C.c_int32), ("gamma", C.c_double), ("global_nx", C.c_int64),
+                ("scale_exp", C.c_int32 * 6)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -184,6 +196,11 @@ SIGNATURES = {
     "armon_hip_exact_norms_reset": (_ci, [_vp, _dp]),
     "armon_hip_exact_norms": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ExactSpec), _dp]),
     "armon_hip_exact_fill": (_ci, [_vp, _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6 + [C.POINTER(ExactSpec)]),
+    "armon_hip_history_create": (_ci, [_vp, _ci, _ci, C.POINTER(_vp)]),
+    "armon_hip_history_destroy": (_ci, [_vp, _vp]),
+    "armon_hip_history_set_gauges": (_ci, [_vp, _vp, C.POINTER(_i64), _ci]),
+    "armon_hip_history_sample": (_ci, [_vp, _vp, _ci, C.POINTER(HistorySpec), _i64, _ci, _i64, _i64] + [_dp] * 4 + [_i64] * 6),
+    "armon_hip_history_read": (_ci, [_vp, _vp, _ci, _ci, _dp, _dp]),
     "armon_hip_sweep": (_ci, [_vp, C.POINTER(SweepDesc)]),
     "armon_hip_dt_state_step": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
     "armon_hip_dt_state_step_f32": (_ci, [_vp, _vp, _vp, _dbl, _dbl, _i64, _ci, _dbl]),
@@ -253,6 +270,7 @@ def _add_f32_signatures():
     SIGNATURES["armon_hip_profile_bounds_f32"] = SIGNATURES["armon_hip_profile_bounds"]
     SIGNATURES["armon_hip_exact_norms_f32"] = SIGNATURES["armon_hip_exact_norms"]
     SIGNATURES["armon_hip_exact_fill_f32"] = SIGNATURES["armon_hip_exact_fill"]
+    SIGNATURES["armon_hip_history_sample_f32"] = SIGNATURES["armon_hip_history_sample"]
     SIGNATURES["armon_hip_tune_placement_f32"] = SIGNATURES["armon_hip_tune_placement"]
     SIGNATURES["armon_hip_choose_placement_f32"] = SIGNATURES["armon_hip_choose_placement"]
 

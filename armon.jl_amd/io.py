@@ -330,3 +330,112 @@ def read_error_norms_file(path):
         t[r[0]] = {c: float(r[1 + k]) for k, c in enumerate(ERROR_NORMS_COLUMNS)}
         t[r[0]]["linf_at"] = None if at == (-1, -1) else at
     return t
+
+
+# ---- run history (history.py): one text file per run, a row per sample --------------------------------------------------
+HISTORY_FMT = "%#24.17e"
+
+
+def _history_header(history, global_grid):
+    """The ``#`` lines of a history file: the format version, the global grid, the six scale exponents, ``ds``, every gauge
+    point with its cell, and the column names."""
+    from .history import COLUMNS, FORMAT_VERSION, GAUGE_VARS
+    lines = [f"# history version={FORMAT_VERSION}",
+             f"# N={int(global_grid[0])},{int(global_grid[1])}",
+             "# scale_exp=" + ",".join(str(s) for s in history.scale_exp),
+             f"# ds={float(history.ds).hex()}"]
+    for i, ((x, y), (gx, gy)) in enumerate(zip(history.gauges, history.gauge_cells)):
+        lines.append(f"# gauge{i}={float(x).hex()},{float(y).hex()},{gx},{gy}")
+    columns = list(COLUMNS) + [f"g{i}_{name}" for i in range(len(history.gauges)) for name in GAUGE_VARS]
+    lines.append("# columns=" + ",".join(columns))
+    return lines
+
+
+def write_history_file(path, history, global_grid):
+    """A history (history.History) as text: the header (``_history_header``), then one row per sample, every column as
+    ``%#24.17e`` (reads back bit for bit). Replaces the file."""
+    with open(path, "w") as f:
+        f.write("\n".join(_history_header(history, global_grid)) + "\n")
+    append_history_rows(path, history, 0)
+
+
+def append_history_rows(path, history, start):
+    """Rows ``start`` … of ``history`` appended to its file."""
+    rows = history.rows(start)
+    if rows:
+        with open(path, "a") as f:
+            for row in rows:
+                f.write(" ".join(HISTORY_FMT % v for v in row) + "\n")
+
+
+def read_history_header(path):
+    """The header fields of a history file → dict field → text, ``scale_exp`` as a tuple of ints."""
+    head = {}
+    with open(path) as f:
+        for line in f:
+            if not line.startswith("#"):
+                break
+            item = line[1:].strip()
+            if item.startswith("history "):
+                item = item[len("history "):]
+            key, _, value = item.partition("=")
+            head[key.strip()] = value.strip()
+    for field in ("version", "N", "scale_exp", "ds", "columns"):
+        if field not in head:
+            from ._lib import solver_error
+            solver_error("config", f"{path} is not a history file: its header has no {field}")
+    head["scale_exp"] = tuple(int(s) for s in head["scale_exp"].split(","))
+    return head
+
+
+def check_history_header(path, head, history, global_grid):
+    """A restart appends to the file of the run it continues only when the header is the one this run would write: a
+    configuration error that names the first field that differs."""
+    from ._lib import solver_error
+    want = read_history_header_lines(_history_header(history, global_grid))
+    fields = [k for k in head if k != "columns"] + [k for k in want if k not in head and k != "columns"] + ["columns"]
+    for field in fields:                        # (the columns last: they follow from the gauges)
+        if head.get(field) != want.get(field):
+            solver_error("config", f"{path} does not continue as this run's history: {field} is {head.get(field)!r} in the file, "
+                                   f"{want.get(field)!r} for this run")
+
+
+def read_history_header_lines(lines):
+    head = {}
+    for line in lines:
+        item = line[1:].strip()
+        if item.startswith("history "):
+            item = item[len("history "):]
+        key, _, value = item.partition("=")
+        head[key.strip()] = value.strip()
+    head["scale_exp"] = tuple(int(s) for s in head["scale_exp"].split(","))
+    return head
+
+
+def truncate_history_file(path, cycle):
+    """Keep the header and the rows up to and including ``cycle``; later rows are dropped."""
+    with open(path) as f:
+        lines = f.readlines()
+    keep = [line for line in lines if line.startswith("#") or (line.strip() and float(line.split()[0]) <= cycle)]
+    with open(path, "w") as f:
+        f.writelines(keep)
+
+
+def read_history_file(path):
+    """→ the dict of ``History.table()``: version, scale_exp, ds, global_nx, gauges, gauge_cells and one fp64 array per column."""
+    head = read_history_header(path)
+    gauges, cells, i = [], [], 0
+    while f"gauge{i}" in head:
+        x, y, gx, gy = head[f"gauge{i}"].split(",")
+        gauges.append((float.fromhex(x), float.fromhex(y)))
+        cells.append((int(gx), int(gy)))
+        i += 1
+    columns = head["columns"].split(",")
+    with open(path) as f:
+        rows = [[float(v) for v in line.split()] for line in f if line.strip() and not line.startswith("#")]
+    data = np.array(rows, dtype=np.float64).reshape(len(rows), len(columns))
+    t = {"version": int(head["version"]), "scale_exp": head["scale_exp"], "ds": float.fromhex(head["ds"]),
+         "global_nx": int(head["N"].split(",")[0]), "gauges": tuple(gauges), "gauge_cells": tuple(cells)}
+    for k, c in enumerate(columns):
+        t[c] = data[:, k].copy()
+    return t

@@ -317,10 +317,20 @@ class TileGroup(NativeGroup):
         self.state_diffs = []
         profiled_at, self.profiles = -1, []   # (and the time of the profiles)
         normed_at, self.error_norms_taken = -1, []   # (and of the error norms)
+        hist, dt_used, self.history = None, 0.0, None
+        if p0.history_step != 0:
+            from .history import HistoryRun
+            hist = HistoryRun(self, p0)       # (the reads of its rings and its file are taken out too: hist.io_ns)
+            hist.start(gdt)
         while gdt.time < maxtime and gdt.cycle < p0.maxcycle:
             self.solver_cycle(last_cycle=S.cycle_ends(p0, gdt))
+            dt_used = float(gdt.current_dt)   # the step this cycle advanced by
             gdt.next_cycle()
+            if hist is not None and gdt.cycle % p0.history_step == 0:
+                hist.sample(gdt, dt_used)     # with the tiles at rest: the strips of a cycle are written on the transfer streams
             if p0.checkpoint_step != 0 and gdt.cycle % p0.checkpoint_step == 0:
+                if hist is not None:
+                    hist.flush()
                 self.wait()
                 t_save = _time.perf_counter_ns()
                 self.save_state(checkpoint_path(p0, gdt.cycle))
@@ -351,7 +361,9 @@ class TileGroup(NativeGroup):
                     break                 # the first difference ends the run (ref @checkpoint, src/solver.jl:40-55)
         self.drain()
         self.wait()
-        solve_ns = _time.perf_counter_ns() - t1 - save_ns
+        solve_ns = _time.perf_counter_ns() - t1 - save_ns - (hist.io_ns if hist is not None else 0)
+        if hist is not None:
+            hist.finish(gdt, dt_used)
         if p0.checkpoint_at_end and saved_at != gdt.cycle:
             self.save_state(checkpoint_path(p0, gdt.cycle))
         if p0.profile_at_end and profiled_at != gdt.cycle:
@@ -373,7 +385,7 @@ class TileGroup(NativeGroup):
         cells = g[0] * g[1]
         return S.SolverStats(float(gdt.time), float(gdt.current_dt), gdt.cycle, solve_ns / 1e9, cells,
                              gdt.cycle * cells / max(solve_ns, 1), data=self, state_diffs=list(self.state_diffs),
-                             profiles=list(self.profiles), error_norms=list(self.error_norms_taken))
+                             profiles=list(self.profiles), error_norms=list(self.error_norms_taken), history=self.history)
 
     # ---- checkpoint / restart (checkpoint.py) ---------------------------------------------------------------------
     def _tiles_at_rest(self):
@@ -422,6 +434,12 @@ class TileGroup(NativeGroup):
         tiles = self._tiles_at_rest()
         return analytic.fill_state(tiles, reference, time=time, samples=samples, coord_range=coord_range,
                                    windows=None if window is None else analytic.tile_windows(tiles, window))
+
+    def history_sample(self, gauges=(), scale_exp=None):
+        """``BlockGrid.history_sample`` of the whole domain: the merge of the tiles' records = the single block's, word for
+        word; each gauge is taken from the tile that owns its cell."""
+        from . import history
+        return history.sample_state(self._tiles_at_rest(), gauges=gauges, scale_exp=scale_exp)
 
     def gather(self, names=("rho", "u", "v", "E", "p")):
         """The real cells of every tile assembled into global (NY, NX) arrays on the host."""

@@ -221,7 +221,8 @@ class ArmonParameters:
                      comparison_atol=0.0, comparison_time_atol=0.0, profile_step=0, profile_kind="x", profile_bins=None,
                      profile_width=1, profile_centre=None, profile_dr=None, profile_file="profile", profile_at_end=False,
                      error_norms_step=0, error_norms_at_end=False, error_norms_samples=1, error_norms_file="error_norms",
-                     start_from_exact=None, **options):
+                     start_from_exact=None, history_step=0, history_file="history", history_gauges=(), history_capacity=256,
+                     history_scale_exp=None, **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
         ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart).
@@ -239,7 +240,16 @@ class ArmonParameters:
         test case at the run's time (analytic.py) is written to ``<output_dir>/<error_norms_file>_<cycle:06d>.txt`` and listed
         in ``SolverStats.error_norms``; ``error_norms_samples``: 1, 2 or 4 points per cell and axis for the cell means of the
         solution; ``error_norms_at_end``: one when the run stops. ``start_from_exact=t0``: the state is filled with the exact
-        solution at ``t0 > 0`` and the clock starts there, so that a convergence study skips the start-up error of the jump."""
+        solution at ``t0 > 0`` and the clock starts there, so that a convergence study skips the start-up error of the jump.
+        ``history_step=k``: the run history (history.py) — a row of exact global sums, extrema with their cells and gauge
+        values for the initial state, after every k completed cycles (0 = off) and for the cycle the run stops at, in
+        ``<output_dir>/<history_file>.txt`` and in ``SolverStats.history``; a single block enqueues each sample behind its
+        cycle and never waits for it. ``history_gauges=[(x, y), ...]``: at most 64 points inside the domain whose cell's rho, u,
+        v, E, p are recorded with every row; ``history_capacity``: the slots of the device-resident ring, read back when it is
+        full (1 .. 65536); ``history_scale_exp``: six exponents instead of the default scale (``history.default_scale``). With
+        ``restart_from`` an existing file whose header matches keeps its rows up to the checkpoint's cycle and is appended
+        to. None of ``history_file``, ``history_gauges``, ``history_capacity``, ``history_scale_exp`` has an effect while
+        ``history_step`` is 0, but each is checked."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
         if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
             solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
@@ -339,6 +349,32 @@ class ArmonParameters:
             if self.test.name in NO_CLOSED_FORM:
                 solver_error("config", f"error_norms_step / error_norms_at_end / start_from_exact need a test case with an exact "
                                        f"solution: {self.test.name} has no closed form")
+        if isinstance(history_step, bool) or not isinstance(history_step, (numbers.Integral, np.integer)) or history_step < 0:
+            solver_error("config", f"history_step must be an integer >= 0, got {history_step!r}")
+        self.history_step = int(history_step)
+        self.history_file = str(history_file)
+        if not self.history_file or "/" in self.history_file:
+            solver_error("config", f"history_file is a file name inside output_dir, got {history_file!r}")
+        if isinstance(history_capacity, bool) or not isinstance(history_capacity, (numbers.Integral, np.integer)) \
+                or not 1 <= history_capacity <= 65536:
+            solver_error("config", f"history_capacity must be an integer in [1, 65536], got {history_capacity!r}")
+        self.history_capacity = int(history_capacity)
+        from . import history as _history
+        try:
+            points = [tuple(pt) for pt in history_gauges]
+            good = all(len(pt) == 2 and not any(isinstance(c, bool) for c in pt) and all(np.isfinite(float(c)) for c in pt) for pt in points)
+        except (TypeError, ValueError):
+            good = False
+        if not good:
+            solver_error("config", f"history_gauges takes a list of (x, y) points, got {history_gauges!r}")
+        if len(points) > _history.MAX_GAUGES:
+            solver_error("config", f"history_gauges: {len(points)} points, at most {_history.MAX_GAUGES}")
+        self.history_gauges = tuple((float(x), float(y)) for x, y in points)
+        _history.gauge_cells(self, self.history_gauges)         # a point outside the domain is refused here, not in the run
+        self.history_scale_exp = None if history_scale_exp is None else _history.check_scale(history_scale_exp)
+        if self.history_step != 0 and self.use_MPI:
+            solver_error("config", "history_step is not supported for ranks of a process group (use_MPI=true): "
+                                   "one block or an in-process tile group only")
         self.silent = silent
         self.output_dir, self.output_file = output_dir, output_file
         self.write_output, self.write_ghosts = write_output, write_ghosts

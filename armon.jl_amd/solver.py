@@ -38,6 +38,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     state_diffs: list = field(default_factory=list)     # (cycle, compare.StateDiff) of compare_step / compare_at_end
     profiles: list = field(default_factory=list)        # (cycle, profile.Profile) of profile_step / profile_at_end
     error_norms: list = field(default_factory=list)     # (cycle, time, analytic.ErrorNorms or None: no solution at that time) of error_norms_step / error_norms_at_end
+    history: object = None                               # history.History of history_step
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -169,6 +170,7 @@ class BlockGrid:
         self.state_diffs = []                  # (cycle, StateDiff) of the run's compare_step / compare_at_end
         self.profiles = []                     # (cycle, Profile) of the run's profile_step / profile_at_end
         self.error_norms_taken = []            # (cycle, time, ErrorNorms) of the run's error_norms_step / error_norms_at_end
+        self.history = None                    # History of the run's history_step
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -421,6 +423,14 @@ class BlockGrid:
         self.params.wait()
         return analytic.fill_state([(self.params, self)], reference, time=time, samples=samples, coord_range=coord_range,
                                    windows=None if window is None else [tuple(window)])
+
+    def history_sample(self, gauges=(), scale_exp=None):
+        """One sample of the run history of this block's state, reduced on the device (history.py states the rule) →
+        ``(history.HistoryRecord, gauge values (gauges, 5))``. ``gauges``: ``(x, y)`` points; ``scale_exp=None``: the default
+        scale of this state."""
+        from . import history
+        self.params.wait()
+        return history.sample_state([(self.params, self)], gauges=gauges, scale_exp=scale_exp)
 
     def real_view(self, a):
         g = self.size.ghosts
@@ -974,6 +984,8 @@ def graph_cycles_usable(params):
         return False                    # and a profile taken
     if params.exact_solution:
         return False                    # and error norms taken, or a start from the exact solution
+    if params.history_step != 0:
+        return False                    # and a history sample enqueued behind a cycle
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
@@ -1180,6 +1192,11 @@ def time_loop(params, grid):
     grid.state_diffs = []
     profiled_at, grid.profiles = -1, []   # (and the time of the profiles)
     normed_at, grid.error_norms_taken = -1, []   # (and of the error norms)
+    hist, dt_used, grid.history = None, 0.0, None
+    if params.history_step != 0:
+        from .history import HistoryRun
+        hist = HistoryRun(grid, params)   # (the reads of its ring and its file are taken out too: hist.io_ns)
+        hist.start(gdt)                   # the row of the initial state, unless the run continues another
     while gdt.time < maxtime and gdt.cycle < params.maxcycle:
         ends = cycle_ends(params, gdt)
         # animation frames (ref :373-378) are written after next_cycle! when (cycle - 1) % animation_step == 0; the fused
@@ -1187,7 +1204,10 @@ def time_loop(params, grid):
         frame_due = params.animation_step != 0 and gdt.cycle % params.animation_step == 0
         if solver_cycle(params, grid, last_cycle=ends or frame_due):
             break
+        dt_used = float(gdt.current_dt)   # the step this cycle advanced by
         gdt.next_cycle()
+        if hist is not None and gdt.cycle % params.history_step == 0:
+            hist.sample(gdt, dt_used)     # enqueued behind the cycle: no wait
         if frame_due:
             from .io import write_animation_frame
             params.wait()
@@ -1202,6 +1222,8 @@ def time_loop(params, grid):
                       f"|ΔM| = {dM:#8.6g}%, |ΔE| = {dE:#8.6g}%")
         if params.checkpoint_step != 0 and gdt.cycle % params.checkpoint_step == 0:
             from .checkpoint import checkpoint_path
+            if hist is not None:
+                hist.flush()              # a restart from this checkpoint finds every row up to it in the file
             params.wait()
             t_save = _time.perf_counter_ns()
             grid.save_state(checkpoint_path(params, gdt.cycle))
@@ -1232,7 +1254,9 @@ def time_loop(params, grid):
                 break                     # the first difference ends the run (ref @checkpoint, src/solver.jl:40-55)
     drain_halo(grid)
     params.wait()   # "Last fence"
-    solve_ns = _time.perf_counter_ns() - t1 - save_ns
+    solve_ns = _time.perf_counter_ns() - t1 - save_ns - (hist.io_ns if hist is not None else 0)
+    if hist is not None:
+        hist.finish(gdt, dt_used)
     if params.checkpoint_at_end and saved_at != gdt.cycle:
         from .checkpoint import checkpoint_path
         grid.save_state(checkpoint_path(params, gdt.cycle))
@@ -1280,6 +1304,7 @@ def armon(params):
     stats.state_diffs = list(grid.state_diffs)
     stats.profiles = list(grid.profiles)
     stats.error_norms = list(grid.error_norms_taken)
+    stats.history = grid.history
     if params.return_data:
         stats.data = grid
     return stats

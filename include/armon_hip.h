@@ -471,6 +471,76 @@ ARMON_API int armon_hip_exact_fill_f32(armon_ctx*, int64_t row_length, int nghos
         float* rho, float* u, float* v, float* E, int64_t col0, int64_t row0, int64_t wnx,
         int64_t wny, int64_t global_col0, int64_t global_row0, const armon_exact_spec* spec);
 
+/* ---- run history: exact global sums, extrema with their cells and point gauges, sampled into a device-resident ring (no
+ * reference counterpart; csrc/history.hip) ---- */
+/* One sample of a window: 40 words = 320 B. Every field merges by integer addition or by a pair minimum / maximum, so the
+ * record of a domain is the merge of the records of its parts, word for word, whatever the split, the launch shape, the
+ * alignment or the ghost width. Sums are three signed limbs as in armon_profile_bin: value = (s[0] + s[1] 2^32 + s[2] 2^64)
+ * 2^scale_exp[k]; no limb overflows while fewer than 2^31 cells are merged. An extremum is a pair (order key of the fp64 value
+ * as in armon_profile_bin, g = gy * global_nx + gx of the cell): a minimum takes the smaller key, a maximum the larger, and
+ * equal keys the smaller g, so the pair does not depend on the order the cells are visited in. While n == 0 the minima are
+ * (UINT64_MAX, UINT64_MAX) and the maxima (0, UINT64_MAX): the neutral elements. */
+enum { ARMON_HISTORY_RHO_MIN = 0, ARMON_HISTORY_RHO_MAX = 1, ARMON_HISTORY_P_MIN = 2, ARMON_HISTORY_P_MAX = 3,
+       ARMON_HISTORY_E_MIN = 4, ARMON_HISTORY_E_MAX = 5, ARMON_HISTORY_Q2_MAX = 6, ARMON_HISTORY_MACH2_MAX = 7 };
+typedef struct {
+    uint64_t n;             /* cells added                                              (sum) */
+    uint64_t n_bad;         /* cells refused, see armon_hip_history_sample              (sum) */
+    int64_t  sum[6][3];     /* rho, rho u, rho v, rho E, (0.5 rho) q2, p: three signed limbs each   (sum, limb by limb, no carry) */
+    uint64_t ext[8][2];     /* ARMON_HISTORY_*: (order key, g)                          (pair min / max) */
+    uint64_t reserved[4];   /* zero */
+} armon_history_record;
+typedef struct {
+    int32_t eos, reserved;  /* ARMON_EOS_* */
+    double  gamma;          /* perfect gas */
+    int64_t global_nx;      /* row length of the global grid: positions are g = gy * global_nx + gx */
+    int32_t scale_exp[6];   /* s_k: quantum of sum k is 2^s_k, -4096 <= s_k <= 4096 */
+} armon_history_spec;
+#define ARMON_HISTORY_MAX_GAUGES 64
+typedef struct armon_history armon_history;
+
+/* A ring of `capacity` (1 .. 65536) slots on the context's device, each one armon_history_record followed by 5 x max_gauges
+ * (0 .. ARMON_HISTORY_MAX_GAUGES) fp64 words, with the reduction scratch of the sample pass (36 words per workgroup, sized
+ * here once: the pass never touches the context's own scratch, which may move and holds the dt partials of the fused sweep),
+ * the gauge table and a pinned landing zone for armon_hip_history_read. Destroy it before the context. */
+ARMON_API int armon_hip_history_create(armon_ctx*, int capacity, int max_gauges, armon_history** out);
+ARMON_API int armon_hip_history_destroy(armon_ctx*, armon_history*);
+/* The cells of the n <= max_gauges gauges as linear indices row * wnx + col INTO THE WINDOW later samples are given, -1 = not in
+ * that window (the gauge's five words are then written as 0). Synchronises the stream; a sample refuses a cell outside its window. */
+ARMON_API int armon_hip_history_set_gauges(armon_ctx*, armon_history*, const int64_t* cells, int n);
+
+/* WRITE the sample of the real cells [col0, col0 + wnx) x [row0, row0 + wny) of one block into slot `slot` of the ring (what
+ * the slot held is lost). Block, window, (global_col0, global_row0) and their checks are those of armon_hip_profile. Also
+ * refused (ARMON_ERR_INVALID_ARG, nothing written): a NULL pointer, a handle of another context, a slot outside [0, capacity),
+ * an unknown eos, a perfect gas whose gamma is not finite and > 1, global_nx < global_col0 + wnx, a scale_exp outside
+ * [-4096, 4096], a gauge cell >= wnx wny. `spec` is HOST memory, read before the call returns.
+ * Per cell at the global position (gx, gy), all arithmetic in fp64 whatever the data type (fp32 values are converted
+ * first), one IEEE operation per operation written, correctly rounded division:
+ *   q2     = u u + v v,  e = E - 0.5 q2
+ *   p, c   the EOS of this cell's (rho, E, u, v) evaluated IN THE DATA TYPE with the operations of the EOS kernels, then
+ *          converted to fp64. No p vector is read.
+ *   terms  t0 = rho, t1 = rho u, t2 = rho v, t3 = rho E, t4 = (0.5 rho) q2, t5 = p
+ *   Q_k    = round-half-even(t_k / 2^s_k), an exact integer; limbs as in armon_hip_profile.
+ *   m      = 0 when q2 == 0, q2 / (c c) otherwise: the square of the Mach number (+inf where c c == 0).
+ *   ext    rho, p and e enter a minimum and a maximum, q2 and m a maximum, each with g = gy * global_nx + gx.
+ *   bad    any of rho, u, v, E, e, c or a t_k not finite, or a |Q_k| >= 2^95: the cell adds 1 to n_bad and nothing else.
+ * Internal energy is not summed: with scale_exp[3] == scale_exp[4] it is sum[3] - sum[4], exactly.
+ * Then the gauges: for each gauge with a cell, (double)rho, (double)u, (double)v, (double)E and (double)p of that cell, p by the
+ * same EOS, as the five words of the gauge in the slot.
+ * No ghost cell is read, no atomics; two launches on the context's stream, no host synchronisation: the slot holds the
+ * sample once the stream has reached it (armon_hip_history_read waits for that). */
+ARMON_API int armon_hip_history_sample(armon_ctx*, armon_history*, int slot, const armon_history_spec* spec, int64_t row_length,
+        int nghost, int64_t nx, int64_t ny, const double* rho, const double* u, const double* v, const double* E, int64_t col0,
+        int64_t row0, int64_t wnx, int64_t wny, int64_t global_col0, int64_t global_row0);
+ARMON_API int armon_hip_history_sample_f32(armon_ctx*, armon_history*, int slot, const armon_history_spec* spec, int64_t row_length,
+        int nghost, int64_t nx, int64_t ny, const float* rho, const float* u, const float* v, const float* E, int64_t col0,
+        int64_t row0, int64_t wnx, int64_t wny, int64_t global_col0, int64_t global_row0);
+
+/* Slots [first_slot, first_slot + count) -> records_host[count] and gauges_host[count][max_gauges][5] (either may be NULL):
+ * ONE device-to-host copy behind everything enqueued so far and ONE stream synchronisation. The library does not track which
+ * slots were written since the last read: the caller does. */
+ARMON_API int armon_hip_history_read(armon_ctx*, armon_history*, int first_slot, int count, armon_history_record* records_host,
+        double* gauges_host);
+
 /* ---- fp32 variants (ref data_type=Float32, src/parameters.jl:185): same kernels, float arrays and scalars ---- */
 typedef struct {
     float *x, *y, *rho, *u, *v, *E, *p, *c, *g, *us, *ps, *work_1, *work_2, *work_3, *work_4, *mask;
