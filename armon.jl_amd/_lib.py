@@ -116,6 +116,12 @@ class HistorySpec(C.Structure):
                 ("scale_exp", C.c_int32 * 6)]
 
 
+class DeriveSpec(C.Structure):
+    """armon_derive_spec — the planes of a derived-field pass (include/armon_hip.h, armon_hip_derive)."""
+    _fields_ = [("nq", C.c_int32), ("quantity", C.c_int32 * 8), ("reduce", C.c_int32 * 8), ("eos", C.c_int32),
+                ("neighbours", C.c_int32), ("gamma", C.c_double), ("dx", C.c_double), ("dy", C.c_double)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -185,6 +191,7 @@ SIGNATURES = {
                                   C.POINTER(_i64 * 2), C.POINTER(_dbl * 2), C.POINTER(_dbl * 2),
                                   _dbl, C.POINTER(BlockDataPtrs)]),
     "armon_hip_coarsen": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 6),
+    "armon_hip_derive": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 4 + [C.POINTER(DeriveSpec), _dp]),
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),
     "armon_hip_state_pack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
     "armon_hip_state_unpack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
@@ -266,6 +273,7 @@ def _add_f32_signatures():
         SIGNATURES["armon_hip_" + name + "_f32"] = SIGNATURES["armon_hip_" + name]
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
+    SIGNATURES["armon_hip_derive_f32"] = SIGNATURES["armon_hip_derive"]
     SIGNATURES["armon_hip_profile_f32"] = SIGNATURES["armon_hip_profile"]
     SIGNATURES["armon_hip_profile_bounds_f32"] = SIGNATURES["armon_hip_profile_bounds"]
     SIGNATURES["armon_hip_exact_norms_f32"] = SIGNATURES["armon_hip_exact_norms"]

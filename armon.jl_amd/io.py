@@ -439,3 +439,66 @@ def read_history_file(path):
     for k, c in enumerate(columns):
         t[c] = data[:, k].copy()
     return t
+
+
+# ---- in-situ images (derived.py) -------------------------------------------------------------------------------------------
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+
+
+def _png_chunk(kind, payload):
+    import struct
+    import zlib
+    return struct.pack(">I", len(payload)) + kind + payload + struct.pack(">I", zlib.crc32(kind + payload) & 0xffffffff)
+
+
+def write_png_gray8(path, img):
+    """An 8-bit greyscale PNG of the ``(height, width)`` uint8 array ``img`` (row 0 = the top row of the picture), written with
+    the standard library only: IHDR, one IDAT of the zlib-compressed rows (each behind a filter byte 0), IEND."""
+    import struct
+    import zlib
+    img = np.asarray(img)
+    if img.dtype != np.uint8 or img.ndim != 2 or img.shape[0] < 1 or img.shape[1] < 1:
+        raise ValueError(f"write_png_gray8 takes a non-empty (height, width) uint8 array, got {img.dtype} {img.shape}")
+    h, w = img.shape
+    rows = np.zeros((h, w + 1), dtype=np.uint8)         # filter type 0 (None) in front of every row
+    rows[:, 1:] = img
+    with open(path, "wb") as f:
+        f.write(PNG_SIGNATURE)
+        f.write(_png_chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 0, 0, 0, 0)))
+        f.write(_png_chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)))
+        f.write(_png_chunk(b"IEND", b""))
+    return path
+
+
+def read_png_chunks(path):
+    """``[(kind, payload, crc_ok)]`` of every chunk of a PNG file (the signature is checked)."""
+    import struct
+    import zlib
+    data = open(path, "rb").read()
+    if data[:8] != PNG_SIGNATURE:
+        raise ValueError(f"{path} is not a PNG file")
+    chunks, at = [], 8
+    while at < len(data):
+        n, = struct.unpack(">I", data[at:at + 4])
+        kind, payload = data[at + 4:at + 8], data[at + 8:at + 8 + n]
+        crc, = struct.unpack(">I", data[at + 8 + n:at + 12 + n])
+        chunks.append((kind, payload, crc == (zlib.crc32(kind + payload) & 0xffffffff)))
+        at += 12 + n
+    return chunks
+
+
+def read_png_gray8(path):
+    """What ``write_png_gray8`` wrote → the ``(height, width)`` uint8 array. Only 8-bit greyscale, no interlace, filter 0."""
+    import struct
+    import zlib
+    chunks = read_png_chunks(path)
+    if not chunks or chunks[0][0] != b"IHDR" or chunks[-1][0] != b"IEND" or not all(ok for _, _, ok in chunks):
+        raise ValueError(f"{path}: a damaged PNG file (chunk order or CRC)")
+    w, h, depth, colour, comp, filt, lace = struct.unpack(">IIBBBBB", chunks[0][1])
+    if (depth, colour, comp, filt, lace) != (8, 0, 0, 0, 0):
+        raise ValueError(f"{path}: only 8-bit greyscale PNG files without interlace are read")
+    raw = zlib.decompress(b"".join(p for k, p, _ in chunks if k == b"IDAT"))
+    rows = np.frombuffer(raw, dtype=np.uint8).reshape(h, w + 1)
+    if rows[:, 0].any():
+        raise ValueError(f"{path}: only rows of filter type 0 are read")
+    return rows[:, 1:].copy()

@@ -317,6 +317,7 @@ class TileGroup(NativeGroup):
         self.state_diffs = []
         profiled_at, self.profiles = -1, []   # (and the time of the profiles)
         normed_at, self.error_norms_taken = -1, []   # (and of the error norms)
+        imaged_at, self.images = -1, []       # (and of the image frames)
         hist, dt_used, self.history = None, 0.0, None
         if p0.history_step != 0:
             from .history import HistoryRun
@@ -343,6 +344,13 @@ class TileGroup(NativeGroup):
                 profile_run(self, p0, gdt)
                 save_ns += _time.perf_counter_ns() - t_save
                 profiled_at = gdt.cycle
+            if p0.image_step != 0 and gdt.cycle % p0.image_step == 0:
+                from .derived import image_run
+                self.wait()
+                t_save = _time.perf_counter_ns()
+                image_run(self, p0, gdt)
+                save_ns += _time.perf_counter_ns() - t_save
+                imaged_at = gdt.cycle
             if p0.error_norms_step != 0 and gdt.cycle % p0.error_norms_step == 0:
                 from .analytic import error_norms_run
                 self.wait()
@@ -369,6 +377,9 @@ class TileGroup(NativeGroup):
         if p0.profile_at_end and profiled_at != gdt.cycle:
             from .profile import profile_run
             profile_run(self, p0, gdt)
+        if p0.image_at_end and imaged_at != gdt.cycle:
+            from .derived import image_run
+            image_run(self, p0, gdt)
         if p0.error_norms_at_end and normed_at != gdt.cycle:
             from .analytic import error_norms_run
             error_norms_run(self, p0, gdt)
@@ -385,7 +396,8 @@ class TileGroup(NativeGroup):
         cells = g[0] * g[1]
         return S.SolverStats(float(gdt.time), float(gdt.current_dt), gdt.cycle, solve_ns / 1e9, cells,
                              gdt.cycle * cells / max(solve_ns, 1), data=self, state_diffs=list(self.state_diffs),
-                             profiles=list(self.profiles), error_norms=list(self.error_norms_taken), history=self.history)
+                             profiles=list(self.profiles), error_norms=list(self.error_norms_taken), history=self.history,
+                             images=list(self.images))
 
     # ---- checkpoint / restart (checkpoint.py) ---------------------------------------------------------------------
     def _tiles_at_rest(self):
@@ -440,6 +452,36 @@ class TileGroup(NativeGroup):
         word; each gauge is taken from the tile that owns its cell."""
         from . import history
         return history.sample_state(self._tiles_at_rest(), gauges=gauges, scale_exp=scale_exp)
+
+    def derive(self, quantities, factor=1, reduce="mean"):
+        """``BlockGrid.derive`` of the whole domain. The tiles come to rest, ``rho, u, v, E`` are exchanged along both axes so
+        that the first ghost layer of every side with a neighbour holds that tile's cells (ghost contents at a cycle boundary
+        are not part of the state: every sweep refreshes what it reads), each tile runs the kernel with the bits of those sides
+        set, and the coarse planes are assembled into the GLOBAL coarse grid like ``coarsen`` (same alignment rule). Central
+        differences across tile edges, exact per-cell arithmetic and the fixed summation order: the planes equal the single
+        block's bit for bit. → dict name → ``(cny, cnx)`` array, plus ``x``, ``y``."""
+        from . import derived
+        from .parameters import check_coarsen_alignment, normalize_coarsen_factor
+        derived.normalize_request(quantities, reduce)          # (a bad request is refused before anything moves)
+        f = normalize_coarsen_factor(factor)
+        if f is None:
+            _lib.solver_error("config", "derive needs a factor >= 1")
+        for p in self.params:
+            check_coarsen_alignment(p, f)
+        tiles = self._tiles_at_rest()
+        for axis in (Axis.X, Axis.Y):
+            self.exchange(sides_along(axis), S.STATE_VARS)
+        self.wait()
+        res = derived.derive_state(tiles, quantities, factor=f, reduce=reduce)
+        cnx, cny = res[next(iter(res))].shape[::-1]
+        for k in ("x", "y"):
+            res[k] = np.empty((cny, cnx), dtype=self.root.data_type)
+        for p, g in tiles:
+            x, y = g.coarse_coordinates(f)
+            ox, oy = (p.N_origin[0] - 1) // f[0], (p.N_origin[1] - 1) // f[1]
+            res["x"][oy:oy + x.shape[0], ox:ox + x.shape[1]] = x
+            res["y"][oy:oy + y.shape[0], ox:ox + y.shape[1]] = y
+        return res
 
     def gather(self, names=("rho", "u", "v", "E", "p")):
         """The real cells of every tile assembled into global (NY, NX) arrays on the host."""

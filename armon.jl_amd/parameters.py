@@ -222,7 +222,8 @@ class ArmonParameters:
                      profile_width=1, profile_centre=None, profile_dr=None, profile_file="profile", profile_at_end=False,
                      error_norms_step=0, error_norms_at_end=False, error_norms_samples=1, error_norms_file="error_norms",
                      start_from_exact=None, history_step=0, history_file="history", history_gauges=(), history_capacity=256,
-                     history_scale_exp=None, **options):
+                     history_scale_exp=None, image_step=0, image_at_end=False, image_quantity="grad_rho", image_reduce=None,
+                     image_coarsen=None, image_transfer=None, image_range=None, image_file="image", **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
         ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart).
@@ -249,7 +250,16 @@ class ArmonParameters:
         full (1 .. 65536); ``history_scale_exp``: six exponents instead of the default scale (``history.default_scale``). With
         ``restart_from`` an existing file whose header matches keeps its rows up to the checkpoint's cycle and is appended
         to. None of ``history_file``, ``history_gauges``, ``history_capacity``, ``history_scale_exp`` has an effect while
-        ``history_step`` is 0, but each is checked."""
+        ``history_step`` is 0, but each is checked.
+        ``image_step=k``: after every k completed cycles (0 = off) a greyscale PNG frame of each derived field of
+        ``image_quantity`` (a name of ``derived.QUANTITIES`` or a list of them), computed and reduced on the device
+        (derived.py), is written to ``<output_dir>/<image_file>_<quantity>_<cycle:06d>.png`` and listed in
+        ``SolverStats.images``; ``image_at_end``: one when the run stops. ``image_reduce``: ``"mean" | "max" | "min"`` or a
+        dict quantity → name (None: max for ``grad_rho``, mean otherwise); ``image_coarsen``: the factor ``f | (fx, fy)``
+        (None: ``output_coarsen`` if set, else the smallest power of two that brings the longer side to at most 2048
+        pixels); ``image_transfer``: ``"linear" | "log" | "schlieren"`` or a dict quantity → name (None: schlieren for
+        ``grad_rho``, linear otherwise); ``image_range=(lo, hi)``: the values of black and white (None: the frame's own
+        finite minimum and maximum)."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
         if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
             solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
@@ -375,6 +385,52 @@ class ArmonParameters:
         if self.history_step != 0 and self.use_MPI:
             solver_error("config", "history_step is not supported for ranks of a process group (use_MPI=true): "
                                    "one block or an in-process tile group only")
+        from . import derived as _derived
+        if isinstance(image_step, bool) or not isinstance(image_step, (numbers.Integral, np.integer)) or image_step < 0:
+            solver_error("config", f"image_step must be an integer >= 0, got {image_step!r}")
+        self.image_step = int(image_step)
+        if not isinstance(image_at_end, (bool, np.bool_)):
+            solver_error("config", f"image_at_end must be True or False, got {image_at_end!r}")
+        self.image_at_end = bool(image_at_end)
+        if not isinstance(image_quantity, (str, tuple, list)) or not all(isinstance(q, str) for q in image_quantity):
+            solver_error("config", f"image_quantity takes a name or a list of names of {_derived.QUANTITIES}, got {image_quantity!r}")
+        if image_reduce is not None and not isinstance(image_reduce, (str, dict)):
+            solver_error("config", f"image_reduce takes a name of {_derived.REDUCTIONS} or a dict quantity -> name, got {image_reduce!r}")
+        names = (image_quantity,) if isinstance(image_quantity, str) else tuple(image_quantity)
+        default_reduce = {q: "max" if q == "grad_rho" else "mean" for q in names}
+        if isinstance(image_reduce, dict):
+            image_reduce = {**{q: m for q, m in default_reduce.items() if q not in image_reduce}, **image_reduce}
+        self.image_quantity, modes = _derived.normalize_request(names, default_reduce if image_reduce is None else image_reduce)
+        self.image_reduce = dict(zip(self.image_quantity, modes))
+        if image_transfer is None:
+            image_transfer = {}
+        elif isinstance(image_transfer, str):
+            image_transfer = {q: image_transfer for q in self.image_quantity}
+        elif not isinstance(image_transfer, dict):
+            solver_error("config", f"image_transfer takes a name of {_derived.TRANSFERS} or a dict quantity -> name, got {image_transfer!r}")
+        for q, t in image_transfer.items():
+            if q not in self.image_quantity or t not in _derived.TRANSFERS:
+                solver_error("config", f"image_transfer: {q!r} -> {t!r}: a quantity of image_quantity and one of {_derived.TRANSFERS}")
+        self.image_transfer = {q: image_transfer.get(q, "schlieren" if q == "grad_rho" else "linear") for q in self.image_quantity}
+        if image_range is not None:
+            try:
+                good = len(image_range) == 2 and not any(isinstance(c, bool) for c in image_range) and \
+                    all(np.isfinite(float(c)) for c in image_range) and float(image_range[0]) < float(image_range[1])
+            except (TypeError, ValueError):
+                good = False
+            if not good:
+                solver_error("config", f"image_range takes two finite values lo < hi, got {image_range!r}")
+        self.image_range = None if image_range is None else (float(image_range[0]), float(image_range[1]))
+        self._image_coarsen = None if image_coarsen is None else normalize_coarsen_factor(image_coarsen)
+        if image_coarsen is not None and self._image_coarsen is None:
+            solver_error("config", f"image_coarsen takes factors >= 1 (None for the default), got {image_coarsen!r}")
+        if not isinstance(image_file, str) or not image_file or "/" in image_file:
+            solver_error("config", f"image_file is a file name inside output_dir, got {image_file!r}")
+        self.image_file = image_file
+        self.state_image = self.image_step != 0 or self.image_at_end        # any frame taken during the run
+        if self.state_image and self.use_MPI:
+            solver_error("config", "image_step / image_at_end are not supported for ranks of a process group (use_MPI=true): "
+                                   "one block or an in-process tile group only")
         self.silent = silent
         self.output_dir, self.output_file = output_dir, output_file
         self.write_output, self.write_ghosts = write_output, write_ghosts
@@ -411,6 +467,11 @@ class ArmonParameters:
             if self.write_ghosts:
                 solver_error("config", "output_coarsen averages real cells only: it cannot be combined with write_ghosts")
             check_coarsen_alignment(self, self.output_coarsen)
+        # the factor of the image frames (image_coarsen, consumed by _init_output): its default needs output_coarsen
+        from .derived import default_image_factor
+        self.image_factor = self._image_coarsen or self.output_coarsen or default_image_factor(self.global_grid)
+        if self.state_image:
+            check_coarsen_alignment(self, self.image_factor)
         if device_id is None:
             device_id = int(os.environ.get("LOCAL_RANK", "0")) if self.use_MPI else 0
         self.device_id = int(device_id)

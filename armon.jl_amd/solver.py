@@ -39,6 +39,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     profiles: list = field(default_factory=list)        # (cycle, profile.Profile) of profile_step / profile_at_end
     error_norms: list = field(default_factory=list)     # (cycle, time, analytic.ErrorNorms or None: no solution at that time) of error_norms_step / error_norms_at_end
     history: object = None                               # history.History of history_step
+    images: list = field(default_factory=list)          # paths of the frames of image_step / image_at_end
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -171,6 +172,7 @@ class BlockGrid:
         self.profiles = []                     # (cycle, Profile) of the run's profile_step / profile_at_end
         self.error_norms_taken = []            # (cycle, time, ErrorNorms) of the run's error_norms_step / error_norms_at_end
         self.history = None                    # History of the run's history_step
+        self.images = []                       # paths of the frames of the run's image_step / image_at_end
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -408,6 +410,19 @@ class BlockGrid:
         self.params.wait()
         return profile.profile_state([(self.params, self)], kind, bins=bins, width=width, centre=centre, dr=dr, with_p=with_p,
                                      scale_exp=scale_exp)
+
+    def derive(self, quantities, factor=1, reduce="mean"):
+        """Derived flow fields of this block's state — names of ``derived.QUANTITIES`` (rho, p, e, speed, mach, grad_rho,
+        vorticity, divergence) — computed on the device and reduced over the coarse cells of ``coarsen(factor)``
+        (armon_hip_derive; derived.py states the rule) → dict name → ``(cny, cnx)`` array, plus ``x``, ``y`` from
+        ``coarse_coordinates``. ``reduce``: ``"mean" | "max" | "min"``, or a dict quantity → name. The block is the whole
+        domain: one-sided differences at its edges, no ghost cell is read. Only the coarse planes cross PCIe."""
+        from . import derived
+        from .parameters import normalize_coarsen_factor
+        self.params.wait()
+        res = derived.derive_state([(self.params, self)], quantities, factor=factor, reduce=reduce, neighbours=[0])
+        res["x"], res["y"] = self.coarse_coordinates(normalize_coarsen_factor(factor))
+        return res
 
     def error_norms(self, reference=None, time=None, samples=1, coord_range=None, window=None, scale_exp=None):
         """The distance of this block's state from an exact solution, reduced on the device (analytic.py states the rule and the
@@ -986,6 +1001,8 @@ def graph_cycles_usable(params):
         return False                    # and error norms taken, or a start from the exact solution
     if params.history_step != 0:
         return False                    # and a history sample enqueued behind a cycle
+    if params.state_image:
+        return False                    # and an image frame rendered
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
@@ -1192,6 +1209,7 @@ def time_loop(params, grid):
     grid.state_diffs = []
     profiled_at, grid.profiles = -1, []   # (and the time of the profiles)
     normed_at, grid.error_norms_taken = -1, []   # (and of the error norms)
+    imaged_at, grid.images = -1, []       # (and of the image frames)
     hist, dt_used, grid.history = None, 0.0, None
     if params.history_step != 0:
         from .history import HistoryRun
@@ -1236,6 +1254,13 @@ def time_loop(params, grid):
             profile_run(grid, params, gdt)
             save_ns += _time.perf_counter_ns() - t_save
             profiled_at = gdt.cycle
+        if params.image_step != 0 and gdt.cycle % params.image_step == 0:
+            from .derived import image_run
+            params.wait()
+            t_save = _time.perf_counter_ns()
+            image_run(grid, params, gdt)
+            save_ns += _time.perf_counter_ns() - t_save
+            imaged_at = gdt.cycle
         if params.error_norms_step != 0 and gdt.cycle % params.error_norms_step == 0:
             from .analytic import error_norms_run
             params.wait()
@@ -1263,6 +1288,9 @@ def time_loop(params, grid):
     if params.profile_at_end and profiled_at != gdt.cycle:
         from .profile import profile_run
         profile_run(grid, params, gdt)
+    if params.image_at_end and imaged_at != gdt.cycle:
+        from .derived import image_run
+        image_run(grid, params, gdt)
     if params.error_norms_at_end and normed_at != gdt.cycle:
         from .analytic import error_norms_run
         error_norms_run(grid, params, gdt)
@@ -1305,6 +1333,7 @@ def armon(params):
     stats.profiles = list(grid.profiles)
     stats.error_norms = list(grid.error_norms_taken)
     stats.history = grid.history
+    stats.images = list(grid.images)
     if params.return_data:
         stats.data = grid
     return stats

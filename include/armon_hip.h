@@ -251,6 +251,45 @@ ARMON_API int armon_hip_coarsen(armon_ctx*, int64_t row_length, int nghost, int6
 ARMON_API int armon_hip_gather_strided(armon_ctx*, int64_t n_cells, int nvars, const double* const* vars,
         int64_t start, int64_t stride, int64_t count, double* out_dev);
 
+/* ---- derived flow fields for in-situ images (no reference counterpart; csrc/derive.hip) ---- */
+enum { ARMON_DERIVE_RHO, ARMON_DERIVE_P, ARMON_DERIVE_EINT, ARMON_DERIVE_SPEED, ARMON_DERIVE_MACH,
+       ARMON_DERIVE_GRAD_RHO, ARMON_DERIVE_VORTICITY, ARMON_DERIVE_DIVERGENCE, ARMON_DERIVE_COUNT };
+enum { ARMON_REDUCE_MEAN, ARMON_REDUCE_MAX, ARMON_REDUCE_MIN };
+typedef struct {
+    int32_t nq, quantity[8], reduce[8]; /* 1 .. 8 planes: ARMON_DERIVE_* and ARMON_REDUCE_* of each                */
+    int32_t eos;            /* ARMON_EOS_*                                                                           */
+    int32_t neighbours;     /* bit 0 left, 1 right, 2 bottom (row -1), 3 top: the FIRST ghost layer of that side holds
+                               the neighbour tile's cells                                                            */
+    double gamma, dx, dy;   /* perfect gas: its gamma; the cell sizes, converted to the data type                    */
+} armon_derive_spec;        /* HOST memory, read before the call returns */
+
+/* One pass over the real cells of a block (described as in armon_hip_coarsen): per cell up to 8 selected quantities from
+ * rho, u, v, E, each reduced over the fx x fy coarse cells of armon_hip_coarsen (same cell -> coarse cell map, same
+ * clamping of a factor larger than the grid) into the dense planes out_dev[nq][cny][cnx] of the data type. No p vector is
+ * read: pressure and sound speed are the EOS of the cell itself, as in armon_hip_profile. 32 B read per fp64 cell, plus the
+ * two rows around each chunk of 64 rows when a stencil quantity is selected.
+ *   PER CELL, all arithmetic in the data type, one IEEE operation per operation written, IEEE division and square root:
+ *     e = E - 0.5 (u u + v v);  p, c = the EOS (perfect gas: p = (gamma - 1) rho e, c = sqrt((gamma p) / rho))
+ *     speed = sqrt(u u + v v);  mach = speed / c
+ *     d_x f = (f_R - f_L) / (T(w) dx): f_R = f[i+1] if that cell exists, else f[i]; f_L likewise; w = how many of the two
+ *             exist; w = 0: the derivative is 0 and nothing is divided; d_y likewise with dy. A neighbour exists if it is a
+ *             real cell of this block or lies in the first ghost layer of a side whose bit of `neighbours` is set: central
+ *             differences inside and across tile edges, one-sided ones at the edge of the global domain.
+ *     grad_rho = sqrt(gx gx + gy gy);  vorticity = d_x v - d_y u;  divergence = d_x u + d_y v
+ *   Only the four edge-adjacent ghost strips of flagged sides are read: no corner, no deeper layer, no ghost cell of an
+ *   unflagged side.
+ *   REDUCTION: ARMON_REDUCE_MEAN = the sum, in the summation order of armon_hip_coarsen (csrc/coarsen.hip), divided by the
+ *   number of cells covered: a function of the values covered only, not of the launch shape, the alignment path, the ghost
+ *   width or the tile split. MAX / MIN: plain, +0 above -0. In all three a NaN among the covered values gives the canonical
+ *   quiet NaN.
+ * fx a power of two <= 64 with fy <= 64 is one kernel and needs no scratch. Any other factor takes two kernels through the
+ * context's reduction scratch, which must hold nq * nx * ceil(ny / min(fy, 64)) elements of the data type; it grows, stays
+ * and is refused inside a capture exactly as for armon_hip_coarsen. Refused (ARMON_ERR_INVALID_ARG, before any launch,
+ * nothing written): a NULL pointer, nq outside 1 .. 8, an unknown quantity, reduction or EOS, dx or dy not finite and > 0,
+ * factors < 1, a bit of `neighbours` set with nghost == 0, and the block checks of armon_hip_coarsen. Async on the stream. */
+ARMON_API int armon_hip_derive(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int64_t fx, int64_t fy,
+        const double* rho, const double* u, const double* v, const double* E, const armon_derive_spec* spec, double* out_dev);
+
 /* ---- checkpoint / restart (no reference counterpart; csrc/checkpoint.hip) ---- */
 /* Move a window of REAL cells between the vectors of one block and a dense buffer, and digest it, in one pass. The block has
  * rows of `row_length` elements, `nghost` ghost layers and nx x ny real cells; the window is the real cells
@@ -582,6 +621,8 @@ ARMON_API int armon_hip_init_test_f32(armon_ctx*, armon_range, int test, int64_t
         const float origin[2], const float dX[2], float sedov_r, const armon_block_data_f32* data);
 ARMON_API int armon_hip_coarsen_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int64_t fx, int64_t fy,
         const float* rho, const float* u, const float* v, const float* E, const float* p, float* out_dev);
+ARMON_API int armon_hip_derive_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int64_t fx, int64_t fy,
+        const float* rho, const float* u, const float* v, const float* E, const armon_derive_spec* spec, float* out_dev);
 ARMON_API int armon_hip_gather_strided_f32(armon_ctx*, int64_t n_cells, int nvars, const float* const* vars,
         int64_t start, int64_t stride, int64_t count, float* out_dev);
 ARMON_API int armon_hip_state_pack_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
