@@ -22,7 +22,7 @@ from types import SimpleNamespace
 import numpy as np
 
 from ._lib import ExactSpec, check, solver_error
-from .profile import EDGE, KINDS, MASK, SCALE_LIMIT, from_limbs, limbs, quantise
+from .profile import EDGE, KINDS, MASK, SCALE_LIMIT, from_limbs, quantise_limbs
 
 RIEMANN, TABLE = 0, 1
 VARS = ("rho", "un", "ut", "p")
@@ -381,37 +381,6 @@ def cell_vars(spec, rho, u, v, E, gx, gy):
     return r64, un, ut, p
 
 
-def quantise_array(t, s):
-    """``profile.quantise`` on a whole fp64 array → ``(a, ok)``: a = |Q| as Python ints in an object array where they can be
-    large, uint64 otherwise; ok = False where the value is not finite or |Q| >= 2^95."""
-    t = np.ascontiguousarray(t, dtype=np.float64)
-    b = t.view(np.uint64)
-    ef = ((b >> np.uint64(52)) & np.uint64(0x7ff)).astype(np.int64)
-    frac = b & np.uint64((1 << 52) - 1)
-    m = np.where(ef > 0, frac | np.uint64(1 << 52), frac)
-    sh = np.where(ef > 0, ef, 1) - 1075 - int(s)
-    ok = ef != 0x7ff
-    a = np.zeros(t.shape, dtype=np.uint64)
-    up = ok & (sh >= 0) & (m != 0)
-    small = up & (sh <= 10)
-    a[small] = m[small] << sh[small].astype(np.uint64)
-    down = ok & (sh < 0) & (m != 0)
-    r = np.minimum(-sh[down], 63).astype(np.uint64)
-    md = m[down]
-    q, rem, half = md >> r, md & ((np.uint64(1) << r) - np.uint64(1)), np.uint64(1) << (r - np.uint64(1))
-    a[down] = q + ((rem > half) | ((rem == half) & ((q & np.uint64(1)) != 0))).astype(np.uint64)
-    big = up & (sh > 10)
-    if big.any():                               # (only a caller's own, finer scale gets here)
-        a = a.astype(object)
-        for i in zip(*np.nonzero(big)):
-            Q = quantise(float(t[i]), s)
-            if Q is None:
-                ok[i] = False
-            else:
-                a[i] = abs(Q)
-    return a, ok
-
-
 def neutral():
     raw = np.zeros((4, WORDS), dtype=np.uint64)
     raw[:, W_AT] = MASK
@@ -438,8 +407,8 @@ def reference_record(spec, rho, u, v, E, origin=(0, 0), skip=None):
         for k in range(4):
             d = A[k] - B[k]
             sq = d * d
-            q1, ok1 = quantise_array(d, s.scale_exp[k][0])
-            q2, ok2 = quantise_array(sq, s.scale_exp[k][1])
+            *q1, ok1 = quantise_limbs(d, s.scale_exp[k][0])
+            *q2, ok2 = quantise_limbs(sq, s.scale_exp[k][1])
             ok &= ok1 & ok2
             quanta.append((d, q1, q2))
     use = keep & ok
@@ -449,16 +418,10 @@ def reference_record(spec, rho, u, v, E, origin=(0, 0), skip=None):
         d, q1, q2 = quanta[k]
         w = [0] * WORDS
         w[W_N], w[W_BAD] = int(use.sum()), int((keep & ~ok).sum())
-        neg = np.signbit(d[use])
-        for base, a, signed in ((W_D, q1[use], True), (W_ABS, q1[use], False), (W_SQ, q2[use], False)):
-            if a.dtype == np.uint64:            # |Q| < 2^64: the two low limbs of every cell at once, summed exactly (< 2^63)
-                sign = np.where(neg, -1, 1).astype(np.int64) if signed else np.int64(1)
-                w[base] += int(((a & np.uint64(0xffffffff)).astype(np.int64) * sign).sum(dtype=np.int64))
-                w[base + 1] += int(((a >> np.uint64(32)).astype(np.int64) * sign).sum(dtype=np.int64))
-                continue
-            for val, n in zip(a.tolist(), neg.tolist()):
-                for j, l in enumerate(limbs(-val if (signed and n) else val)):
-                    w[base + j] += l
+        sign = np.where(np.signbit(d[use]), -1, 1).astype(np.int64)
+        for base, l, sg in ((W_D, q1, sign), (W_ABS, q1, np.int64(1)), (W_SQ, q2, np.int64(1))):
+            for j in range(3):              # a limb of every cell at once, summed exactly (below 2^63)
+                w[base + j] = int((l[j][use].astype(np.int64) * sg).sum(dtype=np.int64))
         bits = np.abs(d[use]).view(np.uint64)
         w[W_AT] = MASK
         if bits.size and int(bits.max()) != 0:

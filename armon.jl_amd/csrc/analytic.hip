@@ -16,15 +16,11 @@
 // MERGE: integer addition and red::op_pair_max only — associative and commutative, so the records are a function of the state
 // and the spec: not of the launch shape, the alignment path, the ghost width or the decomposition.
 //
-// Launch model (state_compare.hip's): lanes along x, 16 B per lane and vector when every row of the window starts on a 16-B
-// boundary in all four vectors, element-wide accesses by the same lanes otherwise; non-temporal loads, each cell read once,
-// the four loads of an item issued before its arithmetic. At most kPerCu workgroups per CU walk the (row, span) items, span
-// fastest, a wave at a time (a 1-D grid and 64-bit item numbers: a window may have any number of rows). A lane keeps its 46
-// words in registers; wave shuffle -> LDS over the four waves -> one partial of 52 words per workgroup in the context's
-// reduction scratch (ensure_partials) -> k_norm_fold, one workgroup per variable, merges them into out_dev. No atomics.
-#include "common.hpp"
+// Launch: the window walk of window.hpp, the four loads of an item issued before its arithmetic, kPerCu workgroups per CU. A
+// lane keeps its 46 words in registers; wave shuffle -> LDS over the four waves -> one partial of 52 words per workgroup in
+// the context's reduction scratch (ensure_partials) -> k_norm_fold, one workgroup per variable, merges them into out_dev.
+// No atomics.
 #include "exact_sum.hpp"
-#include "reduce.hpp"
 
 #include <cmath>
 
@@ -32,28 +28,28 @@ using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kVars = 4;                    // rho, un, ut, p
 constexpr int kWords = 13;                  // per variable and partial: n, n_bad, 3 x 3 limbs, max_abs, max_abs_at
 constexpr int kPerCu = 2;                   // workgroups per CU: what the registers allow (launch bounds below)
-constexpr unsigned long long kNone = ~0ull;
 
 using exact::u64;
 using exact::u128;
-using exact::wide;
-using exact::bits_of;
-using exact::finite;
-using exact::load_cells;
 using exact::quantise;
+using win::bits_of;
+using win::finite;
+using win::kNone;
+using win::kWave;
+using win::kWavesPerBlock;
+using win::load_cells;
+using win::pick;
+using win::wide;
 
 static_assert(sizeof(armon_exact_norm) == 128, "armon_exact_norm is 16 words");
 
 template <typename T>
 struct ex_args {
     T *rho, *u, *v, *E;
-    int64_t pitch, first;           // row pitch of the vectors; index of the window's first cell in them
-    int64_t wnx, wny, nspan;        // window; spans of 64 lanes x V columns per row
+    win::window w;
     int64_t gx0, gy0;               // global position of the window's first cell
     armon_exact_spec s;
     u64* partials;                  // [gridDim.x][kVars][kWords]
@@ -164,16 +160,6 @@ __device__ __forceinline__ bool cell_vars(const armon_exact_spec& s, T rho_, T u
     return finite(rho) && finite(u) && finite(v) && finite(E) && finite(un) && finite(ut) && finite(t[3]);
 }
 
-// f[c] by selects: the array stays in registers under a loop that is not unrolled
-template <int V, typename T>
-__device__ __forceinline__ T pick(const T f[V], int c)
-{
-    T r = f[0];
-#pragma unroll
-    for (int i = 1; i < V; i++) r = c == i ? f[i] : r;
-    return r;
-}
-
 struct norm_acc {
     u64 n, n_bad;
     long long sum[kVars][3][3];     // [variable][d, |d|, d d][limb]
@@ -219,12 +205,10 @@ k_exact_norms(ex_args<T> a)
     constexpr int V = wide<T>::n;
     __shared__ u64 lds[kWavesPerBlock][kVars * kWords];
     const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + w, nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.wny * a.nspan;
-    const T* __restrict__ rho = a.rho + a.first;
-    const T* __restrict__ u = a.u + a.first;
-    const T* __restrict__ v = a.v + a.first;
-    const T* __restrict__ E = a.E + a.first;
+    const T* __restrict__ rho = a.rho + a.w.first;
+    const T* __restrict__ u = a.u + a.w.first;
+    const T* __restrict__ v = a.v + a.w.first;
+    const T* __restrict__ E = a.E + a.w.first;
     norm_acc acc;
     acc.n = acc.n_bad = 0;
 #pragma unroll
@@ -233,12 +217,10 @@ k_exact_norms(ex_args<T> a)
 #pragma unroll
         for (int j = 0; j < 9; j++) acc.sum[k][j / 3][j % 3] = 0;
     }
-    for (int64_t unit = wave; unit < units; unit += nwaves) {       // wave-uniform
-        const int64_t sp = unit % a.nspan, r = unit / a.nspan;
-        const int64_t x = (sp * kWave + lane) * V, left = a.wnx - x;
-        if (left <= 0) continue;                                    // columns past the window are never touched
+    win::walk<V>(a.w, [&](int64_t r, int64_t x, int64_t left) {
+        if (left <= 0) return;
         T fr[V], fu[V], fv[V], fE[V];                               // the four loads are issued before the first arithmetic
-        const int64_t at = r * a.pitch + x;
+        const int64_t at = r * a.w.pitch + x;
         load_cells<T, WIDE>(rho + at, left >= V, left, fr);
         load_cells<T, WIDE>(u + at, left >= V, left, fu);
         load_cells<T, WIDE>(v + at, left >= V, left, fv);
@@ -251,7 +233,7 @@ k_exact_norms(ex_args<T> a)
             if (!cell_centre(a.s, gx, gy, rx, ry, rr)) continue;
             add_cell<T>(a.s, pick<V>(fr, c), pick<V>(fu, c), pick<V>(fv, c), pick<V>(fE, c), gx, gy, rx, ry, rr, acc);
         }
-    }
+    });
     // lane -> wave -> LDS -> one partial per workgroup
     const u64 n = red::wave_reduce<red::op_sum>(acc.n), n_bad = red::wave_reduce<red::op_sum>(acc.n_bad);
 #pragma unroll
@@ -335,15 +317,16 @@ k_exact_fill(ex_args<T> a)
 {
     constexpr int V = wide<T>::n;
     typedef typename wide<T>::type VT;
+    T* __restrict__ dst[4] = {a.rho + a.w.first, a.u + a.w.first, a.v + a.w.first, a.E + a.w.first};
+    // (the loop of win::walk written out: as a callable it changes this kernel's occupancy)
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave, nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.wny * a.nspan;
-    T* __restrict__ dst[4] = {a.rho + a.first, a.u + a.first, a.v + a.first, a.E + a.first};
+    const int64_t units = a.w.wny * a.w.nspan;
     for (int64_t unit = wave; unit < units; unit += nwaves) {
-        const int64_t sp = unit % a.nspan, r = unit / a.nspan;
-        const int64_t x = (sp * kWave + lane) * V, left = a.wnx - x;
+        const int64_t r = unit / a.w.nspan;
+        const auto [x, left] = win::lane_column<V>(a.w, unit % a.w.nspan, lane);
         if (left <= 0) continue;
-        const int64_t at = r * a.pitch + x;                         // at + c < the window's row end for c < left
+        const int64_t at = r * a.w.pitch + x;                         // at + c < the window's row end for c < left
         T val[V][4];
         bool keep[V], all = left >= V;
 #pragma unroll
@@ -378,15 +361,10 @@ int exact_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int64
 {
     ARMON_REQUIRE(ctx != nullptr, "ctx is NULL");
     ARMON_REQUIRE(rho && u && v && E && spec && (FILL || out_dev), "NULL argument");
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
-    ARMON_REQUIRE(col0 >= 0 && row0 >= 0 && wnx >= 1 && wny >= 1 && wnx <= nx - col0 && wny <= ny - row0,
-                  "the window [%lld, %lld) x [%lld, %lld) leaves the real domain %lld x %lld", (long long)col0,
-                  (long long)(col0 + wnx), (long long)row0, (long long)(row0 + wny), (long long)nx, (long long)ny);
-    ARMON_REQUIRE(global_col0 >= 0 && global_row0 >= 0 && global_col0 < (1ll << 40) && global_row0 < (1ll << 40),
-                  "invalid global position: (%lld, %lld)", (long long)global_col0, (long long)global_row0);
+    ex_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, a.w);
+    if (rc == ARMON_OK) rc = win::check_global_cell(global_col0, global_row0);
+    if (rc != ARMON_OK) return rc;
     const armon_exact_spec& s = *spec;
     ARMON_REQUIRE(s.form == ARMON_EXACT_RIEMANN || s.form == ARMON_EXACT_TABLE, "unknown form %d of the exact solution", s.form);
     ARMON_REQUIRE(s.coord == ARMON_PROFILE_X || s.coord == ARMON_PROFILE_Y || s.coord == ARMON_PROFILE_R, "unknown coordinate %d", s.coord);
@@ -408,29 +386,20 @@ int exact_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int64
         for (int j = 0; j < 2; j++)
             ARMON_REQUIRE(s.scale_exp[k][j] >= -4096 && s.scale_exp[k][j] <= 4096, "exact solution: scale_exp[%d][%d] = %d leaves [-4096, 4096]",
                           k, j, s.scale_exp[k][j]);
-    constexpr int V = wide<T>::n;
-    ex_args<T> a;
     a.rho = rho; a.u = u; a.v = v; a.E = E;
-    a.pitch = row_length;
-    a.first = ((int64_t)nghost + row0) * row_length + nghost + col0;
-    a.wnx = wnx; a.wny = wny;
-    a.nspan = (wnx + kWave * V - 1) / (kWave * V);
     a.gx0 = global_col0; a.gy0 = global_row0;
     a.s = s;
     a.partials = nullptr;
     const uintptr_t mis = (uintptr_t)rho | (uintptr_t)u | (uintptr_t)v | (uintptr_t)E;
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0;
-    const int64_t units = a.wny * a.nspan;
-    int64_t blocks = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-    const int64_t max_blocks = (int64_t)ctx->n_cu * kPerCu;
-    if (blocks > max_blocks) blocks = max_blocks;
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n);
+    const int64_t blocks = win::walk_blocks(a.w, (int64_t)ctx->n_cu * kPerCu);
     const dim3 grid((unsigned)blocks), block(kBlock);
     if (FILL) {
         if (wide_ok) hipLaunchKernelGGL((k_exact_fill<T, true>), grid, block, 0, ctx->stream, a);
         else hipLaunchKernelGGL((k_exact_fill<T, false>), grid, block, 0, ctx->stream, a);
         return check_launch("exact_fill");
     }
-    int rc = ensure_partials(ctx, (size_t)kVars * kWords * blocks);  // (doubles and 64-bit words have the same size)
+    rc = ensure_partials(ctx, (size_t)kVars * kWords * blocks);  // (doubles and 64-bit words have the same size)
     if (rc != ARMON_OK) return rc;
     a.partials = reinterpret_cast<u64*>(ctx->partials);
     if (wide_ok) hipLaunchKernelGGL((k_exact_norms<T, true>), grid, block, 0, ctx->stream, a);

@@ -13,15 +13,13 @@
 // sum of the digests of its parts. Each call ADDS its window's digests to `digest_dev[k]` (the caller clears them once), so
 // the bands of a checkpoint accumulate on the device with no host synchronisation.
 //
-// Launch model (coarsen.hip's): lanes along x, 16 B per lane and vector when every row of the window starts on a 16-B
-// boundary in all the vectors and in the dense buffer, element-wide accesses by the same lanes otherwise; a grid of at most
-// 8 workgroups per CU walks the (row, span) items, span fastest. Reduction as in reduce.hpp: lane -> wave shuffle -> LDS over
-// the waves -> one partial per workgroup and variable -> fold kernel. No atomics.
+// Launch: the window walk of window.hpp over the vectors and the dense buffer (16-B rows there need wnx to be a multiple of
+// V), 8 workgroups per CU. Reduction as in reduce.hpp: lane -> wave shuffle -> LDS over the waves -> one partial per
+// workgroup and variable -> fold kernel. No atomics.
 // The partials live in the context's reduction scratch: the first call whose grid needs more of it than the context has
 // (ensure_partials) synchronises the stream once to grow it, and is refused while a captured graph of the context is alive;
 // apart from that the calls never synchronise with the host.
-#include "common.hpp"
-#include "reduce.hpp"
+#include "window.hpp"
 
 using namespace armon;
 
@@ -32,16 +30,13 @@ using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxVars = 8;
 
-template <typename T> struct wide;
-template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ uint64_t bits_of(double v) { return (uint64_t)__double_as_longlong(v); }
-__device__ __forceinline__ uint64_t bits_of(float v) { return (uint64_t)__float_as_uint(v); }
+using win::bits_of;
+using win::kWavesPerBlock;
+using win::load_cells;
+using win::store_cells;
+using win::wide;
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z)
 {
@@ -56,44 +51,10 @@ struct state_args {
     T* vars[kMaxVars];              // pack: read only
     T* dense;                       // [nvars][wny][wnx]; NULL (pack only) = digest only
     unsigned long long* partials;   // [kMaxVars][gridDim.x]
-    int64_t pitch, first;           // row pitch of the vectors; index of the window's first cell in them
-    int64_t wnx, wny, nspan;        // window; spans of 64 lanes x V columns per row
+    win::window w;
     uint64_t g0, NX;                // global index of the window's first cell, global row length
     int nvars;
 };
-
-template <typename T, bool WIDE>
-__device__ __forceinline__ void load_cells(const T* __restrict__ src, bool whole, int64_t left, T f[wide<T>::n])
-{
-    constexpr int V = wide<T>::n;
-    typedef typename wide<T>::type VT;
-    if (WIDE && whole) {
-        const VT* q = reinterpret_cast<const VT*>(src);
-        const VT w = ARMON_CKPT_NT ? __builtin_nontemporal_load(q) : *q;
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = w[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = c < left ? (ARMON_CKPT_NT ? __builtin_nontemporal_load(src + c) : src[c]) : T(0.);
-    }
-}
-
-template <typename T, bool WIDE>
-__device__ __forceinline__ void store_cells(T* __restrict__ dst, bool whole, int64_t left, const T f[wide<T>::n])
-{
-    constexpr int V = wide<T>::n;
-    typedef typename wide<T>::type VT;
-    if (WIDE && whole) {
-        VT w;
-#pragma unroll
-        for (int c = 0; c < V; c++) w[c] = f[c];
-        *reinterpret_cast<VT*>(dst) = w;
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; c++)
-            if (c < left) dst[c] = f[c];
-    }
-}
 
 // One (row, span) item per wave and turn. UNPACK: dense -> vectors; otherwise vectors -> dense (when there is one).
 template <typename T, bool WIDE, bool UNPACK>
@@ -102,31 +63,31 @@ k_state_move(state_args<T> a)
 {
     constexpr int V = wide<T>::n;
     __shared__ unsigned long long lds[kWavesPerBlock];
-    const int lane = threadIdx.x & (kWave - 1);
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-    const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.wny * a.nspan, plane = a.wny * a.wnx;
+    const int64_t plane = a.w.wny * a.w.wnx;
     const bool has_dense = a.dense != nullptr;
     unsigned long long acc[kMaxVars];
 #pragma unroll
     for (int q = 0; q < kMaxVars; q++) acc[q] = 0;
+    // (the loop of win::walk written out: as a callable it changes this kernel's occupancy)
+    const int lane = threadIdx.x & (win::kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / win::kWave;
+    const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock, units = a.w.wny * a.w.nspan;
     for (int64_t unit = wave; unit < units; unit += nwaves) {      // wave-uniform
-        const int64_t s = unit % a.nspan, r = unit / a.nspan;
-        const int64_t x = (s * kWave + lane) * V;                  // the lane's first column of the window
-        if (x >= a.wnx) continue;
-        const int64_t left = a.wnx - x;                            // columns past the window are never touched
+        const int64_t r = unit / a.w.nspan;
+        const auto [x, left] = win::lane_column<V>(a.w, unit % a.w.nspan, lane);
+        if (left <= 0) continue;
         const bool whole = left >= V;
-        const int64_t at = a.first + r * a.pitch + x, dat = r * a.wnx + x;
+        const int64_t at = a.w.first + r * a.w.pitch + x, dat = r * a.w.wnx + x;
         const uint64_t g8 = 8 * (a.g0 + (uint64_t)r * a.NX + (uint64_t)x) + 1;
 #pragma unroll
         for (int q = 0; q < kMaxVars; q++) {
             if (q < a.nvars) {                                     // uniform
                 T f[V];
                 if (UNPACK) {
-                    load_cells<T, WIDE>(a.dense + q * plane + dat, whole, left, f);
+                    load_cells<T, WIDE, ARMON_CKPT_NT>(a.dense + q * plane + dat, whole, left, f);
                     store_cells<T, WIDE>(a.vars[q] + at, whole, left, f);
                 } else {
-                    load_cells<T, WIDE>(a.vars[q] + at, whole, left, f);
+                    load_cells<T, WIDE, ARMON_CKPT_NT>(a.vars[q] + at, whole, left, f);
                     if (has_dense) store_cells<T, WIDE>(a.dense + q * plane + dat, whole, left, f);
                 }
 #pragma unroll
@@ -164,17 +125,10 @@ int state_move_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, 
     ARMON_REQUIRE(ctx != nullptr, "ctx is NULL");
     ARMON_REQUIRE(nvars >= 1 && nvars <= kMaxVars, "nvars = %d: 1 to %d vectors", nvars, kMaxVars);
     ARMON_REQUIRE(vars && digest_dev && (dense_dev || !UNPACK), "NULL argument");
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
-    ARMON_REQUIRE(col0 >= 0 && row0 >= 0 && wnx >= 1 && wny >= 1 && wnx <= nx - col0 && wny <= ny - row0,
-                  "the window [%lld, %lld) x [%lld, %lld) leaves the real domain %lld x %lld", (long long)col0,
-                  (long long)(col0 + wnx), (long long)row0, (long long)(row0 + wny), (long long)nx, (long long)ny);
-    ARMON_REQUIRE(global_first >= 0 && global_nx >= wnx, "invalid global position: first = %lld, row length = %lld",
-                  (long long)global_first, (long long)global_nx);
-    constexpr int V = wide<T>::n;
     state_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, a.w);
+    if (rc == ARMON_OK) rc = win::check_global_index(global_first, global_nx, wnx);
+    if (rc != ARMON_OK) return rc;
     uintptr_t mis = (uintptr_t)dense_dev;
     for (int q = 0; q < kMaxVars; q++) {
         a.vars[q] = q < nvars ? vars[q] : nullptr;
@@ -182,18 +136,12 @@ int state_move_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, 
         mis |= (uintptr_t)a.vars[q];
     }
     a.dense = dense_dev;
-    a.pitch = row_length;
-    a.first = ((int64_t)nghost + row0) * row_length + nghost + col0;
-    a.wnx = wnx; a.wny = wny;
-    a.nspan = (wnx + kWave * V - 1) / (kWave * V);
     a.g0 = (uint64_t)global_first; a.NX = (uint64_t)global_nx;
     a.nvars = nvars;
     // rows of the dense side start wnx apart: it only has 16-B rows when wnx is a multiple of V
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0 && (!dense_dev || wnx % V == 0);
-    const int64_t units = a.wny * a.nspan, max_blocks = (int64_t)ctx->n_cu * 8;
-    int64_t blocks = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > max_blocks) blocks = max_blocks;
-    int rc = ensure_partials(ctx, (size_t)kMaxVars * blocks);      // (doubles and 64-bit words have the same size)
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n) && (!dense_dev || wnx % wide<T>::n == 0);
+    const int64_t blocks = win::walk_blocks(a.w, (int64_t)ctx->n_cu * 8);
+    rc = ensure_partials(ctx, (size_t)kMaxVars * blocks);      // (doubles and 64-bit words have the same size)
     if (rc != ARMON_OK) return rc;
     a.partials = reinterpret_cast<unsigned long long*>(ctx->partials);
     const dim3 grid((unsigned)blocks), block(kBlock);

@@ -19,30 +19,29 @@
 // rows of one coarse row, each lane adds its rows in registers, the columns are combined in the lane and then across lanes
 // (__shfl_xor), the first lane of each coarse cell divides and stores. Any other factor — the same
 // kernel stores the column sums of each row chunk to the context's scratch and a second kernel folds them per coarse cell
-// (a team of min(P, 256) threads per cell). Both walk their work items with a grid of the order of 8 workgroups per CU.
-#include "common.hpp"
+// (a team of min(P, 256) threads per cell). The lanes, the alignment rule and the grid cap (8 workgroups per CU) are those of
+// the window walk (window.hpp) over the whole real domain, with plain loads; the item is a (coarse row, row chunk, span).
+#include "window.hpp"
 
 using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kRowChunk = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxGather = 8;
 
-template <typename T> struct wide;
-template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
+using win::kWave;
+using win::kWavesPerBlock;
+using win::wide;
 
 template <typename T>
 struct coarsen_args {
     const T *rho, *u, *v, *E, *p;   // p may be NULL
     T* out;                         // [5][cny][cnx]
     T* scratch;                     // two-kernel form: [5][cny][nchunk][nx] column sums of each row chunk
-    int64_t pitch, first;           // row pitch; index of the first real cell
-    int64_t nx, ny, fx, fy, cnx, cny;
-    int64_t nchunk, nspan;          // row chunks per coarse row; spans of 64 lanes x V columns per row
+    win::window w;                  // the whole real domain: nx = w.wnx, ny = w.wny
+    int64_t fx, fy, cnx, cny;
+    int64_t nchunk;                 // row chunks per coarse row
     int tree;                       // single-kernel form: width of the column tree (= fx)
 };
 
@@ -75,11 +74,11 @@ k_coarsen_rows(coarsen_args<T> a)
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
     const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.cny * a.nchunk * a.nspan;
+    const int64_t units = a.cny * a.nchunk * a.w.nspan;
     for (int64_t unit = wave; unit < units; unit += nwaves) {      // wave-uniform
-        const int64_t s = unit % a.nspan, jk = unit / a.nspan, k = jk % a.nchunk, J = jk / a.nchunk;
-        const int64_t x = (s * kWave + lane) * V;                  // the lane's first column
-        const int64_t r_end = (J + 1) * a.fy < a.ny ? (J + 1) * a.fy : a.ny;
+        const int64_t s = unit % a.w.nspan, jk = unit / a.w.nspan, k = jk % a.nchunk, J = jk / a.nchunk;
+        const auto [x, left] = win::lane_column<V>(a.w, s, lane);
+        const int64_t r_end = (J + 1) * a.fy < a.w.wny ? (J + 1) * a.fy : a.w.wny;
         const int64_t r_lo = J * a.fy + k * kRowChunk;
         const int64_t r_hi = r_lo + kRowChunk < r_end ? r_lo + kRowChunk : r_end;
         T acc[5][V];
@@ -87,11 +86,11 @@ k_coarsen_rows(coarsen_args<T> a)
         for (int q = 0; q < 5; q++)
 #pragma unroll
             for (int c = 0; c < V; c++) acc[q][c] = T(0.);
-        const bool whole = x + V <= a.nx;
-        if (x < a.nx) {
+        const bool whole = left >= V;
+        if (left > 0) {
 #pragma unroll 4
             for (int64_t r = r_lo; r < r_hi; r++) {
-                const int64_t at = a.first + r * a.pitch + x;
+                const int64_t at = a.w.first + r * a.w.pitch + x;
                 T f[5][V];
                 if (WIDE && whole) {
                     const VT w0 = *reinterpret_cast<const VT*>(rho + at), w1 = *reinterpret_cast<const VT*>(u + at);
@@ -103,7 +102,7 @@ k_coarsen_rows(coarsen_args<T> a)
                 } else {
 #pragma unroll
                     for (int c = 0; c < V; c++) {
-                        const bool in = x + c < a.nx;             // columns past the real domain are ghosts: never read
+                        const bool in = x + c < a.w.wnx;             // columns past the real domain are ghosts: never read
                         f[0][c] = in ? rho[at + c] : T(0.);
                         f[1][c] = in ? u[at + c] : T(0.);
                         f[2][c] = in ? v[at + c] : T(0.);
@@ -140,22 +139,22 @@ k_coarsen_rows(coarsen_args<T> a)
             if ((lane & (lanes - 1)) == 0) {
 #pragma unroll
                 for (int c = 0; c < V; c++) {
-                    if (c % a.tree == 0 && x + c < a.nx) {
+                    if (c % a.tree == 0 && x + c < a.w.wnx) {
                         const int64_t I = (x + c) / a.fx;
-                        const int64_t nc = (I + 1) * a.fx < a.nx ? a.fx : a.nx - I * a.fx;
+                        const int64_t nc = (I + 1) * a.fx < a.w.wnx ? a.fx : a.w.wnx - I * a.fx;
                         const T sums[5] = {acc[0][c], acc[1][c], acc[2][c], acc[3][c], acc[4][c]};
                         store_cell(a, I, J, nc * (r_hi - r_lo), sums);
                     }
                 }
             }
-        } else if (x < a.nx) {
+        } else if (left > 0) {
 #pragma unroll
             for (int q = 0; q < 5; q++) {
                 if (q == 4 && !has_p) break;
-                T* __restrict__ dst = a.scratch + ((q * a.cny + J) * a.nchunk + k) * a.nx + x;
+                T* __restrict__ dst = a.scratch + ((q * a.cny + J) * a.nchunk + k) * a.w.wnx + x;
 #pragma unroll
                 for (int c = 0; c < V; c++)
-                    if (x + c < a.nx) dst[c] = acc[q][c];
+                    if (x + c < a.w.wnx) dst[c] = acc[q][c];
             }
         }
     }
@@ -177,8 +176,8 @@ k_coarsen_cols(coarsen_args<T> a, int team)
         const bool valid = cell < ncell;
         const int64_t I = valid ? cell % a.cnx : 0, J = valid ? cell / a.cnx : 0;
         const int64_t x0 = I * a.fx, y0 = J * a.fy;
-        const int64_t nc = valid ? (x0 + a.fx < a.nx ? a.fx : a.nx - x0) : 0;
-        const int64_t nr = y0 + a.fy < a.ny ? a.fy : a.ny - y0;
+        const int64_t nc = valid ? (x0 + a.fx < a.w.wnx ? a.fx : a.w.wnx - x0) : 0;
+        const int64_t nr = y0 + a.fy < a.w.wny ? a.fy : a.w.wny - y0;
         const int64_t kn = (nr + kRowChunk - 1) / kRowChunk;
         T acc[5] = {T(0.), T(0.), T(0.), T(0.), T(0.)};
         for (int64_t i = t; i < nc; i += team) {
@@ -186,7 +185,7 @@ k_coarsen_cols(coarsen_args<T> a, int team)
             for (int64_t k = 0; k < kn; k++) {
 #pragma unroll
                 for (int q = 0; q < 5; q++)
-                    if (q < 4 || has_p) col[q] += scratch[((q * a.cny + J) * a.nchunk + k) * a.nx + x0 + i];
+                    if (q < 4 || has_p) col[q] += scratch[((q * a.cny + J) * a.nchunk + k) * a.w.wnx + x0 + i];
             }
 #pragma unroll
             for (int q = 0; q < 5; q++) acc[q] += col[q];
@@ -234,38 +233,31 @@ int coarsen_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int
 {
     ARMON_REQUIRE(ctx != nullptr, "ctx is NULL");
     ARMON_REQUIRE(fx >= 1 && fy >= 1, "coarsening factors must be >= 1, got (%lld, %lld)", (long long)fx, (long long)fy);
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
-    ARMON_REQUIRE(rho && u && v && E && out_dev, "NULL array");
-    constexpr int V = wide<T>::n;
-    const bool single = is_pow2(fx) && fx <= kWave && fy <= kRowChunk;
     coarsen_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, 0, 0, nx, ny, a.w);
+    if (rc != ARMON_OK) return rc;
+    ARMON_REQUIRE(rho && u && v && E && out_dev, "NULL array");
+    const bool single = is_pow2(fx) && fx <= kWave && fy <= kRowChunk;
     a.rho = rho; a.u = u; a.v = v; a.E = E; a.p = p;
     a.out = out_dev;
     a.scratch = nullptr;
-    a.pitch = row_length;
-    a.first = (int64_t)nghost * row_length + nghost;
-    a.nx = nx; a.ny = ny;
     // a factor larger than the grid makes one coarse cell along that axis: index arithmetic with the clamped value
     a.fx = single || fx < nx ? fx : nx;
     a.fy = fy < ny ? fy : ny;
     a.cnx = (nx + a.fx - 1) / a.fx;
     a.cny = (ny + a.fy - 1) / a.fy;
     a.nchunk = (a.fy + kRowChunk - 1) / kRowChunk;
-    a.nspan = (nx + kWave * V - 1) / (kWave * V);
     a.tree = single ? (int)fx : 0;
     const uintptr_t mis = (uintptr_t)rho | (uintptr_t)u | (uintptr_t)v | (uintptr_t)E | (uintptr_t)p;
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0;
-    const int64_t units = a.cny * a.nchunk * a.nspan, max_blocks = (int64_t)ctx->n_cu * 8;
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n);
+    const int64_t units = a.cny * a.nchunk * a.w.nspan, max_blocks = (int64_t)ctx->n_cu * 8;
     int64_t blocks = (units + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > max_blocks) blocks = max_blocks;
     if (!single) {
         // one value per real column, row chunk and plane: nx * ceil(ny / min(fy, 64)) * 4 (5 with p) elements — as much as
         // the fields themselves when fy = 1. It stays with the context (include/armon_hip.h says so).
-        const size_t bytes = (size_t)(p ? 5 : 4) * a.cny * a.nchunk * a.nx * sizeof(T);
-        int rc = ensure_partials(ctx, (bytes + sizeof(double) - 1) / sizeof(double));   // grows (and waits) on first need only
+        const size_t bytes = (size_t)(p ? 5 : 4) * a.cny * a.nchunk * a.w.wnx * sizeof(T);
+        rc = ensure_partials(ctx, (bytes + sizeof(double) - 1) / sizeof(double));   // grows (and waits) on first need only
         if (rc != ARMON_OK) return rc;
         a.scratch = reinterpret_cast<T*>(ctx->partials);
     }
@@ -277,7 +269,7 @@ int coarsen_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int
     }
     if (wide_ok) hipLaunchKernelGGL((k_coarsen_rows<T, true, false>), grid, block, 0, ctx->stream, a);
     else hipLaunchKernelGGL((k_coarsen_rows<T, false, false>), grid, block, 0, ctx->stream, a);
-    int rc = check_launch("coarsen_rows");
+    rc = check_launch("coarsen_rows");
     if (rc != ARMON_OK) return rc;
     int team = 1;
     while (team < kBlock && team < fx) team *= 2;

@@ -36,12 +36,13 @@
 // Kernel shape. A wave takes 64 lanes x (16 B of columns) x the rows of one (coarse row, row chunk); each lane marches down
 // its rows with a rolling window of three rows of rho, u, v in registers (each row of a chunk is loaded once, plus the two
 // rows around the chunk: 66 rows read per 64), takes the columns x-1 and x+V from the adjacent lanes with wave shifts (only
-// the two lanes at a span's ends load an extra element) and E for the row it evaluates. 16-B loads where every row of the
-// real domain starts on a 16-B boundary, element loads by the same lanes otherwise. No LDS in the row kernel. It is built
+// the two lanes at a span's ends load an extra element) and E for the row it evaluates. The lanes, the alignment rule and the
+// grid cap (8 workgroups per CU) are those of the window walk (window.hpp) over the whole real domain, with plain loads; the
+// item is a (coarse row, row chunk, span). No LDS in the row kernel. It is built
 // for up to 2 and up to 8 planes and per EOS form (none needed, perfect gas, Bizarrium): 158 to 192 VGPRs in fp64, 2 to 3
 // waves per SIMD — that, not memory, bounds the pass (DESIGN.md §4.9 has the measurements).
-#include "common.hpp"
 #include "physics.hpp"
+#include "window.hpp"
 
 #include <cmath>
 
@@ -49,23 +50,21 @@ using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kRowChunk = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxQ = 8;
 
-template <typename T> struct wide;
-template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
+using win::kWave;
+using win::kWavesPerBlock;
+using win::wide;
 
 template <typename T>
 struct derive_args {
     const T *rho, *u, *v, *E;
     T* out;                         // [nq][cny][cnx]
     T* scratch;                     // two-kernel form: [nq][cny][nchunk][nx] column results of each row chunk
-    int64_t pitch, first;           // row pitch; index of the first real cell
-    int64_t nx, ny, fx, fy, cnx, cny;
-    int64_t nchunk, nspan;          // row chunks per coarse row; spans of 64 lanes x V columns per row
+    win::window w;                  // the whole real domain: nx = w.wnx, ny = w.wny
+    int64_t fx, fy, cnx, cny;
+    int64_t nchunk;                 // row chunks per coarse row
     int tree;                       // single-kernel form: width of the column tree (= fx)
     int nq, quantity[kMaxQ], reduce[kMaxQ];
     int eos, mask;                  // mask: bit Q is set when quantity Q is selected
@@ -127,10 +126,10 @@ __device__ __forceinline__ void load_row(const derive_args<T>& a, int64_t r, int
 {
     constexpr int V = wide<T>::n;
     typedef typename wide<T>::type VT;
-    const bool real = r >= 0 && r < a.ny;
-    const int64_t at = a.first + r * a.pitch + x;
-    const int64_t hi = real ? a.nx + a.right : a.nx;               // columns below `hi` may be read
-    const bool whole = x + V <= a.nx;
+    const bool real = r >= 0 && r < a.w.wny;
+    const int64_t at = a.w.first + r * a.w.pitch + x;
+    const int64_t hi = real ? a.w.wnx + a.right : a.w.wnx;               // columns below `hi` may be read
+    const bool whole = x + V <= a.w.wnx;
     const T* const src[3] = {a.rho, a.u, a.v};
 #pragma unroll
     for (int q = 0; q < 3; q++) {
@@ -144,7 +143,7 @@ __device__ __forceinline__ void load_row(const derive_args<T>& a, int64_t r, int
         }
         w.l[q] = T(0.);
         w.r[q] = T(0.);
-        if (real && lane == 0 && x < a.nx && (x > 0 || a.left)) w.l[q] = src[q][at - 1];
+        if (real && lane == 0 && x < a.w.wnx && (x > 0 || a.left)) w.l[q] = src[q][at - 1];
         if (real && lane == kWave - 1 && x + V < hi) w.r[q] = src[q][at + V];
     }
 }
@@ -154,14 +153,14 @@ __device__ __forceinline__ void load_E(const derive_args<T>& a, int64_t r, int64
 {
     constexpr int V = wide<T>::n;
     typedef typename wide<T>::type VT;
-    const int64_t at = a.first + r * a.pitch + x;
-    if (WIDE && x + V <= a.nx) {
+    const int64_t at = a.w.first + r * a.w.pitch + x;
+    if (WIDE && x + V <= a.w.wnx) {
         const VT t = *reinterpret_cast<const VT*>(a.E + at);
 #pragma unroll
         for (int c = 0; c < V; c++) e[c] = t[c];
     } else {
 #pragma unroll
-        for (int c = 0; c < V; c++) e[c] = x + c < a.nx ? a.E[at + c] : T(0.);
+        for (int c = 0; c < V; c++) e[c] = x + c < a.w.wnx ? a.E[at + c] : T(0.);
     }
 }
 
@@ -189,12 +188,12 @@ k_derive_rows(derive_args<T> a)
     const int lane = threadIdx.x & (kWave - 1);
     const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
     const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.cny * a.nchunk * a.nspan;
+    const int64_t units = a.cny * a.nchunk * a.w.nspan;
     const bool stencil = (a.mask & kStencil) != 0, with_E = (a.mask & kNeedsE) != 0;
     for (int64_t unit = wave; unit < units; unit += nwaves) {      // wave-uniform, and so is everything that shuffles below
-        const int64_t s = unit % a.nspan, jk = unit / a.nspan, k = jk % a.nchunk, J = jk / a.nchunk;
-        const int64_t x = (s * kWave + lane) * V;                  // the lane's first column
-        const int64_t r_end = (J + 1) * a.fy < a.ny ? (J + 1) * a.fy : a.ny;
+        const int64_t s = unit % a.w.nspan, jk = unit / a.w.nspan, k = jk % a.nchunk, J = jk / a.nchunk;
+        const auto [x, left] = win::lane_column<V>(a.w, s, lane);
+        const int64_t r_end = (J + 1) * a.fy < a.w.wny ? (J + 1) * a.fy : a.w.wny;
         const int64_t r_lo = J * a.fy + k * kRowChunk;
         const int64_t r_hi = r_lo + kRowChunk < r_end ? r_lo + kRowChunk : r_end;
         T acc[NQ][V];
@@ -223,7 +222,7 @@ k_derive_rows(derive_args<T> a)
             }
         }
         for (int64_t r = r_lo; r < r_hi; r++) {
-            const bool has_above = stencil && (r + 1 < a.ny || a.top);
+            const bool has_above = stencil && (r + 1 < a.w.wny || a.top);
             if (has_above) load_row<T, WIDE>(a, r + 1, x, lane, above);
             else if (r + 1 < r_hi) load_row<T, WIDE>(a, r + 1, x, lane, above);        // (pointwise quantities only)
             T e_tot[V];
@@ -242,7 +241,7 @@ k_derive_rows(derive_args<T> a)
 #pragma unroll
             for (int c = 0; c < V; c++) {
                 const int64_t col = x + c;
-                const bool in = col < a.nx;
+                const bool in = col < a.w.wnx;
                 const T rho = cur.f[0][c], u = cur.f[1][c], v = cur.f[2][c], E = e_tot[c];
                 T d[ARMON_DERIVE_COUNT];
 #pragma unroll
@@ -259,7 +258,7 @@ k_derive_rows(derive_args<T> a)
                     d[ARMON_DERIVE_MACH] = speed / cs;
                 }
                 if (stencil) {
-                    const bool has_l = col > 0 || a.left, has_r = col + 1 < a.nx || a.right;
+                    const bool has_l = col > 0 || a.left, has_r = col + 1 < a.w.wnx || a.right;
                     T fl[3], fr[3];
 #pragma unroll
                     for (int q = 0; q < 3; q++) {
@@ -311,9 +310,9 @@ k_derive_rows(derive_args<T> a)
             if ((lane & (lanes - 1)) == 0) {
 #pragma unroll
                 for (int c = 0; c < V; c++) {
-                    if (c % a.tree == 0 && x + c < a.nx) {
+                    if (c % a.tree == 0 && x + c < a.w.wnx) {
                         const int64_t I = (x + c) / a.fx;
-                        const int64_t nc = (I + 1) * a.fx < a.nx ? a.fx : a.nx - I * a.fx;
+                        const int64_t nc = (I + 1) * a.fx < a.w.wnx ? a.fx : a.w.wnx - I * a.fx;
                         T res[kMaxQ];
 #pragma unroll
                         for (int q = 0; q < kMaxQ; q++) res[q] = q < NQ ? acc[q < NQ ? q : 0][c] : T(0.);
@@ -321,14 +320,14 @@ k_derive_rows(derive_args<T> a)
                     }
                 }
             }
-        } else if (x < a.nx) {
+        } else if (left > 0) {
 #pragma unroll
             for (int q = 0; q < NQ; q++) {
                 if (q < a.nq) {
-                    T* __restrict__ dst = a.scratch + ((q * a.cny + J) * a.nchunk + k) * a.nx + x;
+                    T* __restrict__ dst = a.scratch + ((q * a.cny + J) * a.nchunk + k) * a.w.wnx + x;
 #pragma unroll
                     for (int c = 0; c < V; c++)
-                        if (x + c < a.nx) dst[c] = acc[q][c];
+                        if (x + c < a.w.wnx) dst[c] = acc[q][c];
                 }
             }
         }
@@ -350,8 +349,8 @@ k_derive_cols(derive_args<T> a, int team)
         const bool valid = cell < ncell;
         const int64_t I = valid ? cell % a.cnx : 0, J = valid ? cell / a.cnx : 0;
         const int64_t x0 = I * a.fx, y0 = J * a.fy;
-        const int64_t nc = valid ? (x0 + a.fx < a.nx ? a.fx : a.nx - x0) : 0;
-        const int64_t nr = y0 + a.fy < a.ny ? a.fy : a.ny - y0;
+        const int64_t nc = valid ? (x0 + a.fx < a.w.wnx ? a.fx : a.w.wnx - x0) : 0;
+        const int64_t nr = y0 + a.fy < a.w.wny ? a.fy : a.w.wny - y0;
         const int64_t kn = (nr + kRowChunk - 1) / kRowChunk;
         T acc[kMaxQ];
 #pragma unroll
@@ -362,7 +361,7 @@ k_derive_cols(derive_args<T> a, int team)
                 if (q < a.nq) {
                     T col = neutral<T>(a.reduce[q]);
                     for (int64_t k = 0; k < kn; k++)
-                        col = combine(a.reduce[q], col, scratch[((q * a.cny + J) * a.nchunk + k) * a.nx + x0 + i]);
+                        col = combine(a.reduce[q], col, scratch[((q * a.cny + J) * a.nchunk + k) * a.w.wnx + x0 + i]);
                     acc[q] = combine(a.reduce[q], acc[q], col);
                 }
             }
@@ -404,10 +403,9 @@ int derive_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
 {
     ARMON_REQUIRE(ctx != nullptr, "ctx is NULL");
     ARMON_REQUIRE(fx >= 1 && fy >= 1, "coarsening factors must be >= 1, got (%lld, %lld)", (long long)fx, (long long)fy);
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
+    derive_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, 0, 0, nx, ny, a.w);
+    if (rc != ARMON_OK) return rc;
     ARMON_REQUIRE(rho && u && v && E && spec && out_dev, "NULL argument");
     const armon_derive_spec& s = *spec;
     ARMON_REQUIRE(s.nq >= 1 && s.nq <= kMaxQ, "derive: nq = %d: 1 to %d quantities", s.nq, kMaxQ);
@@ -416,8 +414,6 @@ int derive_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
     ARMON_REQUIRE(s.neighbours == 0 || nghost >= 1, "derive: neighbours = %d needs a ghost layer, nghost = %d", s.neighbours, nghost);
     ARMON_REQUIRE(std::isfinite(s.dx) && std::isfinite(s.dy) && s.dx > 0 && s.dy > 0 && std::isfinite((T)s.dx) && std::isfinite((T)s.dy) &&
                   (T)s.dx > 0 && (T)s.dy > 0, "derive: dx = %g, dy = %g must be finite and > 0", s.dx, s.dy);
-    constexpr int V = wide<T>::n;
-    derive_args<T> a;
     a.mask = 0;
     for (int q = 0; q < kMaxQ; q++) {
         a.quantity[q] = a.reduce[q] = 0;
@@ -433,16 +429,12 @@ int derive_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
     a.rho = rho; a.u = u; a.v = v; a.E = E;
     a.out = out_dev;
     a.scratch = nullptr;
-    a.pitch = row_length;
-    a.first = (int64_t)nghost * row_length + nghost;
-    a.nx = nx; a.ny = ny;
     // a factor larger than the grid makes one coarse cell along that axis: index arithmetic with the clamped value
     a.fx = single || fx < nx ? fx : nx;
     a.fy = fy < ny ? fy : ny;
     a.cnx = (nx + a.fx - 1) / a.fx;
     a.cny = (ny + a.fy - 1) / a.fy;
     a.nchunk = (a.fy + kRowChunk - 1) / kRowChunk;
-    a.nspan = (nx + kWave * V - 1) / (kWave * V);
     a.tree = single ? (int)fx : 0;
     a.nq = s.nq;
     a.eos = s.eos;
@@ -450,14 +442,14 @@ int derive_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
     a.gamma = (T)s.gamma; a.dx = (T)s.dx; a.dy = (T)s.dy;
     a.dx2 = T(2.) * a.dx; a.dy2 = T(2.) * a.dy;
     const uintptr_t mis = (uintptr_t)rho | (uintptr_t)u | (uintptr_t)v | (uintptr_t)E;
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0;
-    const int64_t units = a.cny * a.nchunk * a.nspan, max_blocks = (int64_t)ctx->n_cu * 8;
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n);
+    const int64_t units = a.cny * a.nchunk * a.w.nspan, max_blocks = (int64_t)ctx->n_cu * 8;
     int64_t blocks = (units + kWavesPerBlock - 1) / kWavesPerBlock;
     if (blocks > max_blocks) blocks = max_blocks;
     if (!single) {
         // one value per real column, row chunk and quantity: nq * nx * ceil(ny / min(fy, 64)) elements (include/armon_hip.h)
-        const size_t bytes = (size_t)a.nq * a.cny * a.nchunk * a.nx * sizeof(T);
-        int rc = ensure_partials(ctx, (bytes + sizeof(double) - 1) / sizeof(double));   // grows (and waits) on first need only
+        const size_t bytes = (size_t)a.nq * a.cny * a.nchunk * a.w.wnx * sizeof(T);
+        rc = ensure_partials(ctx, (bytes + sizeof(double) - 1) / sizeof(double));   // grows (and waits) on first need only
         if (rc != ARMON_OK) return rc;
         a.scratch = reinterpret_cast<T*>(ctx->partials);
     }
@@ -484,7 +476,7 @@ int derive_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
     else ARMON_DERIVE_ROWS(false, false);
 #undef ARMON_DERIVE_ROWS
 #undef ARMON_DERIVE_ROWS_2
-    int rc = check_launch("derive_rows");
+    rc = check_launch("derive_rows");
     if (rc != ARMON_OK) return rc;
     int team = 1;
     while (team < kBlock && team < fx) team *= 2;

@@ -1,12 +1,10 @@
-// exact_sum.hpp — the fixed-point addends of the decomposition-independent sums (profile.hip, analytic.hip) and the lane loads
-// both passes share. A term t is rounded ONCE, on its own, to Q = round-half-even(t / 2^s); |Q| is cut into three limbs below
+// exact_sum.hpp — the fixed-point addends of the decomposition-independent sums (profile.hip, analytic.hip, history.hip).
+// A term t is rounded ONCE, on its own, to Q = round-half-even(t / 2^s); |Q| is cut into three limbs below
 // 2^32, each negated when Q < 0 and each added to its own int64. Everything after the rounding is integer addition, so a
 // sum is a function of its addends only, word for word.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <cstdint>
+#include "window.hpp"
 
 namespace armon {
 namespace exact {
@@ -14,28 +12,7 @@ namespace exact {
 typedef unsigned long long u64;
 typedef unsigned __int128 u128;
 
-template <typename T> struct wide;
-template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ u64 bits_of(double v) { return (u64)__double_as_longlong(v); }
-__device__ __forceinline__ bool finite(double v) { return (bits_of(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-
-// V cells of a row from `src`: one 16-B non-temporal load when WIDE and the lane has all V of them, element loads otherwise
-template <typename T, bool WIDE>
-__device__ __forceinline__ void load_cells(const T* __restrict__ src, bool whole, int64_t left, T f[wide<T>::n])
-{
-    constexpr int V = wide<T>::n;
-    typedef typename wide<T>::type VT;
-    if (WIDE && whole) {
-        const VT w = __builtin_nontemporal_load(reinterpret_cast<const VT*>(src));
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = w[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = c < left ? __builtin_nontemporal_load(src + c) : T(0.);
-    }
-}
+using win::bits_of;
 
 // Q = round-half-even(t / 2^s) → a = |Q|; false when t is not finite or |Q| >= 2^95
 __device__ __forceinline__ bool quantise(double t, int s, u128& a)

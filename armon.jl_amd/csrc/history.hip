@@ -17,15 +17,10 @@
 // between the two belongs to the handle (sized at creation), not to the context: ensure_partials may move the context's
 // while a run is in flight, and the dt partials of the fused sweep live there.
 //
-// Launch model (analytic.hip's): lanes along x, 16 B per lane and vector when every row of the window starts on a 16-B
-// boundary in all four vectors, element-wide accesses by the same lanes otherwise; non-temporal loads, each cell read once,
-// the four loads of an item issued before its arithmetic. At most kPerCu workgroups per CU walk the (row, span) items, span
-// fastest, a wave at a time (a 1-D grid and 64-bit item numbers: a window may have any number of rows). A lane keeps its 36
-// words in registers; wave shuffle -> LDS over the four waves -> one partial of 36 words per workgroup -> k_history_fold,
-// one workgroup, merges them and WRITES the slot, then its first lanes gather the gauges. No atomics.
-#include "common.hpp"
+// Launch: the window walk of window.hpp, the four loads of an item issued before its arithmetic, kPerCu workgroups per CU. A
+// lane keeps its 36 words in registers; wave shuffle -> LDS over the four waves -> one partial of 36 words per workgroup ->
+// k_history_fold, one workgroup, merges them and WRITES the slot, then its first lanes gather the gauges. No atomics.
 #include "exact_sum.hpp"
-#include "reduce.hpp"
 
 #include <cmath>
 
@@ -33,41 +28,36 @@ using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kTerms = 6, kExt = 8;
 constexpr int kSums = 2 + 3 * kTerms;       // n, n_bad, 6 x 3 limbs
 constexpr int kWords = kSums + 2 * kExt;    // words of a partial: 36
 constexpr int kRecWords = 40;               // sizeof(armon_history_record) / 8
 constexpr int kGaugeWords = 5;
 constexpr int kPerCu = 3;                   // workgroups per CU: what 150 to 160 VGPRs allow (launch bounds below)
-constexpr unsigned long long kNone = ~0ull;
 
 using exact::u64;
 using exact::u128;
-using exact::wide;
-using exact::bits_of;
-using exact::finite;
-using exact::load_cells;
 using exact::quantise;
+using red::op_pair_min;
+using red::order_key;
+using win::bits_of;
+using win::finite;
+using win::kNone;
+using win::kWave;
+using win::kWavesPerBlock;
+using win::load_cells;
+using win::pick;
+using win::wide;
 
 static_assert(sizeof(armon_history_record) == kRecWords * 8, "armon_history_record is 40 words");
 static_assert(sizeof(armon_history_spec) == 48, "armon_history_spec is 48 bytes");
 
-__device__ __forceinline__ u64 order_key(double v) { const u64 b = bits_of(v); return b ^ ((b >> 63) ? ~0ull : (1ull << 63)); }
 __device__ __forceinline__ bool is_min_ext(int k) { return k == ARMON_HISTORY_RHO_MIN || k == ARMON_HISTORY_P_MIN || k == ARMON_HISTORY_E_MIN; }
-
-// (key, position) pairs: the smaller key wins, on equal keys the smaller position; neutral (all ones, all ones)
-struct op_pair_min {
-    template <typename T> __device__ static T id() { return T{~0ull, ~0ull}; }
-    template <typename T> __device__ static T f(T a, T b) { return (b.v < a.v || (b.v == a.v && b.at < a.at)) ? b : a; }
-};
 
 template <typename T>
 struct hist_args {
     const T *rho, *u, *v, *E;
-    int64_t pitch, first;           // row pitch of the vectors; index of the window's first cell in them
-    int64_t wnx, wny, nspan;        // window; spans of 64 lanes x V columns per row
+    win::window w;
     int64_t gx0, gy0;               // global position of the window's first cell
     armon_history_spec s;
     u64* partials;                  // [gridDim.x][kWords]
@@ -78,16 +68,6 @@ __device__ __forceinline__ void eos_of(const armon_history_spec& s, T rho, T u, 
 {
     if (s.eos == ARMON_EOS_PERFECT_GAS) phys::perfect_gas<T>((T)s.gamma, rho, E, u, v, p, c);
     else { T g; phys::bizarrium<false, T>(rho, E, u, v, p, c, g); }
-}
-
-// f[c] by selects: the array stays in registers under a loop that is not unrolled
-template <int V, typename T>
-__device__ __forceinline__ T pick(const T f[V], int c)
-{
-    T r = f[0];
-#pragma unroll
-    for (int i = 1; i < V; i++) r = c == i ? f[i] : r;
-    return r;
 }
 
 struct hist_acc {
@@ -131,24 +111,20 @@ k_history(hist_args<T> a)
     constexpr int V = wide<T>::n;
     __shared__ u64 lds[kWavesPerBlock][kWords];
     const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + w, nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.wny * a.nspan;
-    const T* __restrict__ rho = a.rho + a.first;
-    const T* __restrict__ u = a.u + a.first;
-    const T* __restrict__ v = a.v + a.first;
-    const T* __restrict__ E = a.E + a.first;
+    const T* __restrict__ rho = a.rho + a.w.first;
+    const T* __restrict__ u = a.u + a.w.first;
+    const T* __restrict__ v = a.v + a.w.first;
+    const T* __restrict__ E = a.E + a.w.first;
     hist_acc acc;
     acc.n = acc.n_bad = 0;
 #pragma unroll
     for (int k = 0; k < kTerms; k++) acc.sum[k][0] = acc.sum[k][1] = acc.sum[k][2] = 0;
 #pragma unroll
     for (int k = 0; k < kExt; k++) acc.ext[k] = is_min_ext(k) ? red::upair{kNone, kNone} : red::upair{0, kNone};
-    for (int64_t unit = wave; unit < units; unit += nwaves) {       // wave-uniform
-        const int64_t sp = unit % a.nspan, r = unit / a.nspan;
-        const int64_t x = (sp * kWave + lane) * V, left = a.wnx - x;
-        if (left <= 0) continue;                                    // columns past the window are never touched
+    win::walk<V>(a.w, [&](int64_t r, int64_t x, int64_t left) {
+        if (left <= 0) return;
         T fr[V], fu[V], fv[V], fE[V];                               // the four loads are issued before the first arithmetic
-        const int64_t at = r * a.pitch + x;
+        const int64_t at = r * a.w.pitch + x;
         load_cells<T, WIDE>(rho + at, left >= V, left, fr);
         load_cells<T, WIDE>(u + at, left >= V, left, fu);
         load_cells<T, WIDE>(v + at, left >= V, left, fv);
@@ -159,7 +135,7 @@ k_history(hist_args<T> a)
             if (c >= left) break;
             add_cell<T>(a.s, pick<V>(fr, c), pick<V>(fu, c), pick<V>(fv, c), pick<V>(fE, c), g + (u64)c, acc);
         }
-    }
+    });
     // lane -> wave -> LDS -> one partial per workgroup
     {
         u64* row = lds[w];
@@ -296,15 +272,10 @@ int sample_impl(armon_ctx* ctx, armon_history* h, int slot, const armon_history_
     ARMON_REQUIRE(h && rho && u && v && E && spec, "NULL argument");
     ARMON_REQUIRE(h->ctx == ctx, "history: the handle belongs to another context");
     ARMON_REQUIRE(slot >= 0 && slot < h->capacity, "history: slot %d outside the ring of %d", slot, h->capacity);
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
-    ARMON_REQUIRE(col0 >= 0 && row0 >= 0 && wnx >= 1 && wny >= 1 && wnx <= nx - col0 && wny <= ny - row0,
-                  "the window [%lld, %lld) x [%lld, %lld) leaves the real domain %lld x %lld", (long long)col0,
-                  (long long)(col0 + wnx), (long long)row0, (long long)(row0 + wny), (long long)nx, (long long)ny);
-    ARMON_REQUIRE(global_col0 >= 0 && global_row0 >= 0 && global_col0 < (1ll << 40) && global_row0 < (1ll << 40),
-                  "invalid global position: (%lld, %lld)", (long long)global_col0, (long long)global_row0);
+    hist_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, a.w);
+    if (rc == ARMON_OK) rc = win::check_global_cell(global_col0, global_row0);
+    if (rc != ARMON_OK) return rc;
     const armon_history_spec& s = *spec;
     ARMON_REQUIRE(s.eos == ARMON_EOS_PERFECT_GAS || s.eos == ARMON_EOS_BIZARRIUM, "unknown eos %d", s.eos);
     ARMON_REQUIRE(s.eos != ARMON_EOS_PERFECT_GAS || (std::isfinite(s.gamma) && s.gamma > 1), "history: gamma = %g", s.gamma);
@@ -314,29 +285,21 @@ int sample_impl(armon_ctx* ctx, armon_history* h, int slot, const armon_history_
     for (int i = 0; i < h->n_gauges; i++)
         ARMON_REQUIRE(h->cells[i] < wnx * wny, "history: gauge %d sits at cell %lld of a window of %lld", i, (long long)h->cells[i],
                       (long long)(wnx * wny));
-    constexpr int V = wide<T>::n;
-    hist_args<T> a;
     a.rho = rho; a.u = u; a.v = v; a.E = E;
-    a.pitch = row_length;
-    a.first = ((int64_t)nghost + row0) * row_length + nghost + col0;
-    a.wnx = wnx; a.wny = wny;
-    a.nspan = (wnx + kWave * V - 1) / (kWave * V);
     a.gx0 = global_col0; a.gy0 = global_row0;
     a.s = s;
     a.partials = h->partials;
     const uintptr_t mis = (uintptr_t)rho | (uintptr_t)u | (uintptr_t)v | (uintptr_t)E;
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0;
-    const int64_t units = a.wny * a.nspan;
-    int64_t blocks = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > h->max_blocks) blocks = h->max_blocks;
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n);
+    const int64_t blocks = win::walk_blocks(a.w, h->max_blocks);
     const dim3 grid((unsigned)blocks), block(kBlock);
     if (wide_ok) hipLaunchKernelGGL((k_history<T, true>), grid, block, 0, ctx->stream, a);
     else hipLaunchKernelGGL((k_history<T, false>), grid, block, 0, ctx->stream, a);
-    int rc = check_launch("history");
+    rc = check_launch("history");
     if (rc != ARMON_OK) return rc;
     fold_args<T> f;
     f.rho = rho; f.u = u; f.v = v; f.E = E;
-    f.pitch = a.pitch; f.first = a.first; f.wnx = wnx;
+    f.pitch = a.w.pitch; f.first = a.w.first; f.wnx = wnx;
     f.s = s;
     f.partials = h->partials;
     f.n_partials = (int)blocks;

@@ -24,10 +24,10 @@
 // sum of Q's is not the sum of the splits (2^32 and -1 give the limbs (-1, 1, 0), their sum gives (0xffffffff, 0, 0)), so
 // limbs cut from partial sums would depend on which cells a lane happened to see. Same value, other words.
 //
-// Launch model. Lanes along x as in checkpoint.hip's k_state_move: 16 B per lane and vector when every row of the window
-// starts on a 16-B boundary in all four vectors, element-wide accesses by the same lanes otherwise; non-temporal loads, each
-// cell read once, the four loads of a row issued before its first arithmetic. The window is cut into TILES of one span
-// (64 lanes x 16 B) by 32 rows; a workgroup walks a contiguous run of tiles, its four waves taking 8 rows each. The order of
+// Launch. The lanes, the loads and the alignment rule are those of the window walk (window.hpp), the four loads of a row
+// issued before its first arithmetic; the bounds pass is that walk. The main pass has an item of its own: the window is cut
+// into TILES of one span (64 lanes x 16 B) by 32 rows; a workgroup walks a contiguous run of tiles, its four waves taking 8
+// rows each. The order of
 // the tiles follows the kind: down the rows of one span for X and R, along the spans of one row block for Y, so a lane's
 // bin (X) or the wave's (Y) stays the same for as long as possible. A lane sums in registers (21 words) while its bin does
 // not change; when it changes the lane's record goes to a table of 264 bins in LDS (ds atomics: add, min, max on 64-bit
@@ -40,9 +40,7 @@
 // also what the registers allow (148 to 209 VGPRs: 3, or 2 for the larger variants); the grid is what the occupancy query
 // reports for the variant launched. Equal-bin neighbours of R are not combined across lanes before the LDS: a record is 21
 // words, and the ds atomics of lanes in different bins do not serialise.
-#include "common.hpp"
 #include "exact_sum.hpp"
-#include "reduce.hpp"
 
 #include <cmath>
 
@@ -50,8 +48,8 @@ using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
+using win::kWave;
+using win::kWavesPerBlock;
 constexpr int kTileRows = 32, kRowsPerWave = kTileRows / kWavesPerBlock;
 constexpr int kRec = 21;                    // words of a record that are not reserved
 constexpr int kRecWords = 24;               // sizeof(armon_profile_bin) / 8
@@ -61,25 +59,23 @@ constexpr int W_N = 0, W_BAD = 1, W_SUM = 2, W_RHO_MIN = 17, W_RHO_MAX = 18, W_P
 
 using exact::u64;
 using exact::u128;
-using exact::wide;
-using exact::bits_of;
-using exact::finite;
-using exact::load_cells;
 using exact::quantise;
+using red::order_key;
+using win::bits_of;
+using win::finite;
+using win::load_cells;
+using win::wide;
 
 static_assert(sizeof(armon_profile_bin) == kRecWords * 8, "armon_profile_bin is 24 words");
 
-__device__ __forceinline__ u64 order_key(double v) { const u64 b = bits_of(v); return b ^ ((b >> 63) ? ~0ull : (1ull << 63)); }
 __device__ __forceinline__ bool is_min_word(int w) { return w == W_RHO_MIN || w == W_P_MIN; }
 __device__ __forceinline__ bool is_max_word(int w) { return w == W_RHO_MAX || w == W_P_MAX; }
-
-struct op_umax { template <typename X> __device__ static X id() { return X(0); } template <typename X> __device__ static X f(X p, X q) { return q > p ? q : p; } };
 
 template <typename T>
 struct prof_args {
     const T *rho, *u, *v, *E;
-    int64_t pitch, first;           // row pitch of the vectors; index of the window's first cell in them
-    int64_t wnx, wny, nspan, nrb;   // window; spans of 64 lanes x V columns per row; blocks of kTileRows rows
+    win::window w;
+    int64_t nrb;                    // blocks of kTileRows rows
     int64_t gx0, gy0;               // global position of the window's first cell
     armon_profile_spec s;
     u64* bins;                      // [nbins][kRecWords]
@@ -251,17 +247,17 @@ k_profile(prof_args<T> a)
         cur = -1;
     };
     __syncthreads();
-    const int64_t ntiles = a.nspan * a.nrb, per = (ntiles + gridDim.x - 1) / gridDim.x;
+    const int64_t ntiles = a.w.nspan * a.nrb, per = (ntiles + gridDim.x - 1) / gridDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
-    const T* __restrict__ rho = a.rho + a.first;
-    const T* __restrict__ u = a.u + a.first;
-    const T* __restrict__ v = a.v + a.first;
-    const T* __restrict__ E = a.E + a.first;
+    const T* __restrict__ rho = a.rho + a.w.first;
+    const T* __restrict__ u = a.u + a.w.first;
+    const T* __restrict__ v = a.v + a.w.first;
+    const T* __restrict__ E = a.E + a.w.first;
     for (int64_t tile = t0; tile < t1; tile++) {
-        const int64_t sp = KIND == ARMON_PROFILE_Y ? tile % a.nspan : tile / a.nrb;
-        const int64_t rb = KIND == ARMON_PROFILE_Y ? tile / a.nspan : tile % a.nrb;
-        const int64_t xa = sp * kWave * V, xb = xa + kWave * V < a.wnx ? xa + kWave * V : a.wnx;
-        const int64_t ya = rb * kTileRows, yb = ya + kTileRows < a.wny ? ya + kTileRows : a.wny;
+        const int64_t sp = KIND == ARMON_PROFILE_Y ? tile % a.w.nspan : tile / a.nrb;
+        const int64_t rb = KIND == ARMON_PROFILE_Y ? tile / a.w.nspan : tile % a.nrb;
+        const int64_t xa = sp * kWave * V, xb = xa + kWave * V < a.w.wnx ? xa + kWave * V : a.w.wnx;
+        const int64_t ya = rb * kTileRows, yb = ya + kTileRows < a.w.wny ? ya + kTileRows : a.w.wny;
         const int64_t base = tile_base<KIND>(a.s, a.gx0 + xa, a.gx0 + xb - 1, a.gy0 + ya, a.gy0 + yb - 1);
         if (base != table_base) {
             lane_out();
@@ -270,13 +266,13 @@ k_profile(prof_args<T> a)
             __syncthreads();
             table_base = base;
         }
-        const int64_t x = xa + (int64_t)lane * V, left = a.wnx - x;
+        const auto [x, left] = win::lane_column<V>(a.w, sp, lane);
         if (left <= 0) continue;                                    // (no barrier below this line of the loop body)
         for (int i = 0; i < kRowsPerWave; i++) {
             const int64_t r = ya + (int64_t)w * kRowsPerWave + i;
             if (r >= yb) break;
             T fr[V], fu[V], fv[V], fE[V];                           // the four loads are issued before the first arithmetic
-            const int64_t at = r * a.pitch + x;
+            const int64_t at = r * a.w.pitch + x;
             load_cells<T, WIDE>(rho + at, left >= V, left, fr);
             load_cells<T, WIDE>(u + at, left >= V, left, fu);
             load_cells<T, WIDE>(v + at, left >= V, left, fv);
@@ -307,20 +303,23 @@ k_profile_bounds(prof_args<T> a)
 {
     constexpr int V = wide<T>::n;
     __shared__ u64 lds[kWavesPerBlock];
-    const int tid = (int)threadIdx.x, lane = tid & (kWave - 1);
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + tid / kWave, nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.wny * a.nspan;
-    const T* __restrict__ rho = a.rho + a.first;
-    const T* __restrict__ u = a.u + a.first;
-    const T* __restrict__ v = a.v + a.first;
-    const T* __restrict__ E = a.E + a.first;
+    const int tid = (int)threadIdx.x;
+    const T* __restrict__ rho = a.rho + a.w.first;
+    const T* __restrict__ u = a.u + a.w.first;
+    const T* __restrict__ v = a.v + a.w.first;
+    const T* __restrict__ E = a.E + a.w.first;
     u64 top[5] = {0, 0, 0, 0, 0};
+    // (the loop of win::walk written out, lane arithmetic included: the fp64 element-path variant for R sits two registers above
+    // an occupancy step, and the callable and win::lane_column each move it across)
+    const int lane = tid & (kWave - 1);
+    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + tid / kWave, nwaves = (int64_t)gridDim.x * kWavesPerBlock;
+    const int64_t units = a.w.wny * a.w.nspan;
     for (int64_t unit = wave; unit < units; unit += nwaves) {
-        const int64_t sp = unit % a.nspan, r = unit / a.nspan;
-        const int64_t x = (sp * kWave + lane) * V, left = a.wnx - x;
+        const int64_t sp = unit % a.w.nspan, r = unit / a.w.nspan;
+        const int64_t x = (sp * kWave + lane) * V, left = a.w.wnx - x;
         if (left <= 0) continue;
         T fr[V], fu[V], fv[V], fE[V];
-        const int64_t at = r * a.pitch + x;
+        const int64_t at = r * a.w.pitch + x;
         load_cells<T, WIDE>(rho + at, left >= V, left, fr);
         load_cells<T, WIDE>(u + at, left >= V, left, fu);
         load_cells<T, WIDE>(v + at, left >= V, left, fv);
@@ -340,7 +339,7 @@ k_profile_bounds(prof_args<T> a)
     }
 #pragma unroll
     for (int k = 0; k < 5; k++) {
-        const u64 m = red::block_reduce<op_umax, kWavesPerBlock>(top[k], lds, tid);
+        const u64 m = red::block_reduce<red::op_umax, kWavesPerBlock>(top[k], lds, tid);
         if (tid == 0 && m) merge_max(a.bounds + k, m);
     }
 }
@@ -358,15 +357,10 @@ int profile_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int
 {
     ARMON_REQUIRE(ctx != nullptr, "ctx is NULL");
     ARMON_REQUIRE(rho && u && v && E && spec && out_dev, "NULL argument");
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
-    ARMON_REQUIRE(col0 >= 0 && row0 >= 0 && wnx >= 1 && wny >= 1 && wnx <= nx - col0 && wny <= ny - row0,
-                  "the window [%lld, %lld) x [%lld, %lld) leaves the real domain %lld x %lld", (long long)col0,
-                  (long long)(col0 + wnx), (long long)row0, (long long)(row0 + wny), (long long)nx, (long long)ny);
-    ARMON_REQUIRE(global_col0 >= 0 && global_row0 >= 0 && global_col0 < (1ll << 40) && global_row0 < (1ll << 40),
-                  "invalid global position: (%lld, %lld)", (long long)global_col0, (long long)global_row0);
+    prof_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, a.w);
+    if (rc == ARMON_OK) rc = win::check_global_cell(global_col0, global_row0);
+    if (rc != ARMON_OK) return rc;
     const armon_profile_spec& s = *spec;
     ARMON_REQUIRE(s.kind == ARMON_PROFILE_X || s.kind == ARMON_PROFILE_Y || s.kind == ARMON_PROFILE_R, "unknown profile kind %d", s.kind);
     ARMON_REQUIRE(s.eos == -1 || s.eos == ARMON_EOS_PERFECT_GAS || s.eos == ARMON_EOS_BIZARRIUM, "unknown eos %d", s.eos);
@@ -378,21 +372,16 @@ int profile_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int
                       s.dx, s.dy, s.inv_dr, s.cx, s.cy);
     for (int k = 0; k < 5; k++)
         ARMON_REQUIRE(s.scale_exp[k] >= -4096 && s.scale_exp[k] <= 4096, "profile: scale_exp[%d] = %d leaves [-4096, 4096]", k, s.scale_exp[k]);
-    constexpr int V = wide<T>::n;
-    prof_args<T> a;
     a.rho = rho; a.u = u; a.v = v; a.E = E;
-    a.pitch = row_length;
-    a.first = ((int64_t)nghost + row0) * row_length + nghost + col0;
-    a.wnx = wnx; a.wny = wny;
-    a.nspan = (wnx + kWave * V - 1) / (kWave * V);
     a.nrb = (wny + kTileRows - 1) / kTileRows;
     a.gx0 = global_col0; a.gy0 = global_row0;
     a.s = s;
     a.bins = BOUNDS ? nullptr : static_cast<u64*>(out_dev);
     a.bounds = BOUNDS ? static_cast<u64*>(out_dev) : nullptr;
     const uintptr_t mis = (uintptr_t)rho | (uintptr_t)u | (uintptr_t)v | (uintptr_t)E;
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0;
-    const int64_t work = BOUNDS ? (a.wny * a.nspan + kWavesPerBlock - 1) / kWavesPerBlock : a.nspan * a.nrb;
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n);
+    // the bounds pass: a wave per (row, span) item; the main pass: a workgroup per tile
+    const int64_t work = BOUNDS ? (a.w.wny * a.w.nspan + kWavesPerBlock - 1) / kWavesPerBlock : a.w.nspan * a.nrb;
     const dim3 block(kBlock);
     // the grid = what is resident at once of THIS variant (registers allow 2 or 3 workgroups per CU of the main pass, its LDS 3)
 #define ARMON_PROFILE_LAUNCH_1(KERNEL, W, KIND)                                                                 \

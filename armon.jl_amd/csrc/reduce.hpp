@@ -9,6 +9,7 @@ namespace armon {
 namespace red {
 
 constexpr int kWave = 64;
+constexpr unsigned long long kNone = ~0ull;      // the all-ones word: no position, no key
 
 struct op_min { template <typename T> __device__ static T id() { return T(INFINITY); } template <typename T> __device__ static T f(T a, T b) { return phys::mn(a, b); } };
 // maximum of NON-NEGATIVE values, NaN sticks (phys::amax): only the dt/CFL reductions use it, and a NaN in one cell has to
@@ -17,12 +18,25 @@ struct op_max { template <typename T> __device__ static T id() { return T(0.); }
 struct op_sum { template <typename T> __device__ static T id() { return T(0.); } template <typename T> __device__ static T f(T a, T b) { return a + b; } };
 // minimum of unsigned integers (positions; the all-ones word = none)
 struct op_umin { template <typename T> __device__ static T id() { return ~T(0); } template <typename T> __device__ static T f(T a, T b) { return b < a ? b : a; } };
+struct op_umax { template <typename T> __device__ static T id() { return T(0); } template <typename T> __device__ static T f(T a, T b) { return b > a ? b : a; } };
+// the unsigned word whose order is the numerical order of the doubles (-0.0 below +0.0)
+__device__ __forceinline__ unsigned long long order_key(double v)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return b ^ ((b >> 63) ? ~0ull : (1ull << 63));
+}
 // (value, position) pairs of unsigned 64-bit words: the larger value wins, on equal values the smaller position. Associative
 // and commutative; the neutral element is (0, all ones), which is also what a value of 0 carries as its position.
 struct upair { unsigned long long v, at; };
 struct op_pair_max {
     template <typename T> __device__ static T id() { return T{0ull, ~0ull}; }
     template <typename T> __device__ static T f(T a, T b) { return (b.v > a.v || (b.v == a.v && b.at < a.at)) ? b : a; }
+};
+
+// (key, position) pairs: the smaller key wins, on equal keys the smaller position; neutral (all ones, all ones)
+struct op_pair_min {
+    template <typename T> __device__ static T id() { return T{~0ull, ~0ull}; }
+    template <typename T> __device__ static T f(T a, T b) { return (b.v < a.v || (b.v == a.v && b.at < a.at)) ? b : a; }
 };
 
 template <typename T> __device__ __forceinline__ T shfl_down(T v, int off) { return __shfl_down(v, off, kWave); }

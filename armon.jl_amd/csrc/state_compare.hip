@@ -18,16 +18,14 @@
 // the alignment path, the ghost width or the decomposition. Each call MERGES into diff_dev (state_diff_reset writes the
 // neutral element), so the bands of a file accumulate on the device with no host synchronisation.
 //
-// Launch model (checkpoint.hip's k_state_move): lanes along x, 16 B per lane and source when every row of the window starts on
-// a 16-B boundary in all the vectors and in the dense buffer, element-wide accesses by the same lanes otherwise; at most 8
-// workgroups per CU walk the (row, span) items, span fastest; both loads of an item are issued before its first
-// comparison. The variable is the grid's y index: a workgroup keeps the seven accumulators of ONE variable. Reduction as in
-// reduce.hpp: lane -> wave shuffle -> LDS over the waves -> one partial per workgroup -> fold kernel, one workgroup per variable.
+// Launch: the window walk of window.hpp over the vectors and the dense buffer (16-B rows there need wnx to be a multiple of
+// V), 8 workgroups per CU shared by the variables; both loads of an item are issued before its first comparison. The
+// variable is the grid's y index: a workgroup keeps the seven accumulators of ONE variable. Reduction as in reduce.hpp:
+// lane -> wave shuffle -> LDS over the waves -> one partial per workgroup -> fold kernel, one workgroup per variable.
 // The only atomic is the integer add into row_out (order-independent), issued by one lane per item that has a cell out of
 // tolerance. The partials live in the context's reduction scratch (ensure_partials: one synchronisation to grow, refused
 // inside a capture or while a graph of the context is alive).
-#include "common.hpp"
-#include "reduce.hpp"
+#include "window.hpp"
 
 #include <cmath>
 
@@ -39,26 +37,22 @@ using namespace armon;
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxVars = 8;
 constexpr int kWords = 7;                   // per partial: n_bits, n_out, first_out, max_abs, max_abs_at, max_rel, max_rel_at
-constexpr unsigned long long kNone = ~0ull;
 
 typedef unsigned long long u64;
+using win::bits_of;
+using win::finite;
+using win::kNone;
+using win::kWave;
+using win::kWavesPerBlock;
+using win::load_cells;
+using win::wide;
 
-template <typename T> struct wide;
-template <> struct wide<double> { static constexpr int n = 2; typedef double type __attribute__((ext_vector_type(2))); };
-template <> struct wide<float> { static constexpr int n = 4; typedef float type __attribute__((ext_vector_type(4))); };
-
-__device__ __forceinline__ u64 bits_of(double v) { return (u64)__double_as_longlong(v); }
-__device__ __forceinline__ u64 bits_of(float v) { return (u64)__float_as_uint(v); }
 __device__ __forceinline__ double quotient(double n, double d) { return n / d; }
 __device__ __forceinline__ float quotient(float n, float d) { return __fdiv_rn(n, d); }      // correctly rounded whatever the build's default
 __device__ __forceinline__ u64 canonical_nan(double) { return 0x7ff8000000000000ull; }
 __device__ __forceinline__ u64 canonical_nan(float) { return 0x7fc00000ull; }
-__device__ __forceinline__ bool finite(double v) { return (bits_of(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-__device__ __forceinline__ bool finite(float v) { return (bits_of(v) & 0x7f800000ull) != 0x7f800000ull; }
 
 template <typename T>
 struct cmp_args {
@@ -66,27 +60,10 @@ struct cmp_args {
     const T* ref;                   // [nvars][wny][wnx]
     u64* partials;                  // [nvars][gridDim.x][kWords]
     unsigned* row_out;              // [nvars][wny] or NULL
-    int64_t pitch, first;           // row pitch of the vectors; index of the window's first cell in them
-    int64_t wnx, wny, nspan;        // window; spans of 64 lanes x V columns per row
+    win::window w;
     u64 g0, NX;                     // global index of the window's first cell, global row length
     T rtol, atol;
 };
-
-template <typename T, bool WIDE>
-__device__ __forceinline__ void load_cells(const T* __restrict__ src, bool whole, int64_t left, T f[wide<T>::n])
-{
-    constexpr int V = wide<T>::n;
-    typedef typename wide<T>::type VT;
-    if (WIDE && whole) {
-        const VT* q = reinterpret_cast<const VT*>(src);
-        const VT w = ARMON_CMP_NT ? __builtin_nontemporal_load(q) : *q;
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = w[c];
-    } else {
-#pragma unroll
-        for (int c = 0; c < V; c++) f[c] = c < left ? (ARMON_CMP_NT ? __builtin_nontemporal_load(src + c) : src[c]) : T(0.);
-    }
-}
 
 struct cmp_acc {
     u64 n_bits = 0, n_out = 0, first_out = kNone;
@@ -124,22 +101,16 @@ k_state_compare(cmp_args<T> a)
     __shared__ u64 lds[kWavesPerBlock];
     __shared__ red::upair lds_pair[kWavesPerBlock];
     const int lane = threadIdx.x & (kWave - 1), q = blockIdx.y;
-    const int64_t wave = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-    const int64_t nwaves = (int64_t)gridDim.x * kWavesPerBlock;
-    const int64_t units = a.wny * a.nspan;
-    const T* __restrict__ ours = a.vars[q] + a.first;
-    const T* __restrict__ ref = a.ref + (int64_t)q * a.wny * a.wnx;
-    unsigned* row_out = a.row_out ? a.row_out + (int64_t)q * a.wny : nullptr;
+    const T* __restrict__ ours = a.vars[q] + a.w.first;
+    const T* __restrict__ ref = a.ref + (int64_t)q * a.w.wny * a.w.wnx;
+    unsigned* row_out = a.row_out ? a.row_out + (int64_t)q * a.w.wny : nullptr;
     cmp_acc acc;
-    for (int64_t unit = wave; unit < units; unit += nwaves) {       // wave-uniform
-        const int64_t s = unit % a.nspan, r = unit / a.nspan;
-        const int64_t x = (s * kWave + lane) * V;                   // the lane's first column of the window
-        const int64_t left = a.wnx - x;                             // columns past the window are never touched
+    win::walk<V>(a.w, [&](int64_t r, int64_t x, int64_t left) {
         unsigned out = 0;
         if (left > 0) {
             T fa[V], fb[V];                                         // both sources' loads are issued before the first comparison
-            load_cells<T, WIDE>(ours + r * a.pitch + x, left >= V, left, fa);
-            load_cells<T, WIDE>(ref + r * a.wnx + x, left >= V, left, fb);
+            load_cells<T, WIDE, ARMON_CMP_NT>(ours + r * a.w.pitch + x, left >= V, left, fa);
+            load_cells<T, WIDE, ARMON_CMP_NT>(ref + r * a.w.wnx + x, left >= V, left, fb);
             const u64 g = a.g0 + (u64)r * a.NX + (u64)x;
 #pragma unroll
             for (int c = 0; c < V; c++)
@@ -149,7 +120,7 @@ k_state_compare(cmp_args<T> a)
             out = red::wave_reduce<red::op_sum>(out);
             if (lane == 0) atomicAdd(row_out + r, out);
         }
-    }
+    });
     u64* part = a.partials + ((int64_t)q * gridDim.x + blockIdx.x) * kWords;
     const int tid = (int)threadIdx.x;
     const u64 n_bits = red::block_reduce<red::op_sum, kWavesPerBlock>(acc.n_bits, lds, tid);
@@ -210,17 +181,10 @@ int state_compare_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t n
     ARMON_REQUIRE(nvars >= 1 && nvars <= kMaxVars, "nvars = %d: 1 to %d vectors", nvars, kMaxVars);
     ARMON_REQUIRE(vars && ref_dense_dev && diff_dev, "NULL argument");
     ARMON_REQUIRE(rtol >= 0 && atol >= 0, "invalid tolerance: rtol = %g, atol = %g", rtol, atol);     // (a NaN fails both)
-    ARMON_REQUIRE(nx >= 1 && ny >= 1 && nghost >= 0, "invalid block: nx = %lld, ny = %lld, nghost = %d", (long long)nx, (long long)ny, nghost);
-    ARMON_REQUIRE(nx < (1ll << 31) && ny < (1ll << 31), "block too large: nx = %lld, ny = %lld", (long long)nx, (long long)ny);
-    ARMON_REQUIRE(row_length >= nx + 2 * (int64_t)nghost, "the real cells leave the block: row_length = %lld < nx + 2 nghost = %lld",
-                  (long long)row_length, (long long)(nx + 2 * (int64_t)nghost));
-    ARMON_REQUIRE(col0 >= 0 && row0 >= 0 && wnx >= 1 && wny >= 1 && wnx <= nx - col0 && wny <= ny - row0,
-                  "the window [%lld, %lld) x [%lld, %lld) leaves the real domain %lld x %lld", (long long)col0,
-                  (long long)(col0 + wnx), (long long)row0, (long long)(row0 + wny), (long long)nx, (long long)ny);
-    ARMON_REQUIRE(global_first >= 0 && global_nx >= wnx, "invalid global position: first = %lld, row length = %lld",
-                  (long long)global_first, (long long)global_nx);
-    constexpr int V = wide<T>::n;
     cmp_args<T> a;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, a.w);
+    if (rc == ARMON_OK) rc = win::check_global_index(global_first, global_nx, wnx);
+    if (rc != ARMON_OK) return rc;
     uintptr_t mis = (uintptr_t)ref_dense_dev;
     for (int q = 0; q < kMaxVars; q++) {
         a.vars[q] = q < nvars ? vars[q] : nullptr;
@@ -229,21 +193,14 @@ int state_compare_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t n
     }
     a.ref = ref_dense_dev;
     a.row_out = row_out_dev;
-    a.pitch = row_length;
-    a.first = ((int64_t)nghost + row0) * row_length + nghost + col0;
-    a.wnx = wnx; a.wny = wny;
-    a.nspan = (wnx + kWave * V - 1) / (kWave * V);
     a.g0 = (uint64_t)global_first; a.NX = (uint64_t)global_nx;
     a.rtol = (T)rtol; a.atol = (T)atol;
     // rows of the dense side start wnx apart: it only has 16-B rows when wnx is a multiple of V
-    const bool wide_ok = (mis & 15) == 0 && a.first % V == 0 && a.pitch % V == 0 && wnx % V == 0;
+    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n) && wnx % wide<T>::n == 0;
     // the 8 workgroups per CU are shared by the variables
-    const int64_t units = a.wny * a.nspan;
-    int64_t max_blocks = (int64_t)ctx->n_cu * 8 / nvars;
-    if (max_blocks < 1) max_blocks = 1;
-    int64_t blocks = (units + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > max_blocks) blocks = max_blocks;
-    int rc = ensure_partials(ctx, (size_t)kWords * nvars * blocks);   // (doubles and 64-bit words have the same size)
+    const int64_t max_blocks = (int64_t)ctx->n_cu * 8 / nvars;
+    const int64_t blocks = win::walk_blocks(a.w, max_blocks < 1 ? 1 : max_blocks);
+    rc = ensure_partials(ctx, (size_t)kWords * nvars * blocks);   // (doubles and 64-bit words have the same size)
     if (rc != ARMON_OK) return rc;
     a.partials = reinterpret_cast<u64*>(ctx->partials);
     const dim3 grid((unsigned)blocks, (unsigned)nvars), block(kBlock);

@@ -28,7 +28,7 @@ from fractions import Fraction
 import numpy as np
 
 from ._lib import HistorySpec, check, solver_error
-from .profile import MASK, SCALE_LIMIT, from_key, from_limbs, limbs, order_key, quantise  # noqa: F401  (the rule's parts)
+from .profile import MASK, SCALE_LIMIT, from_key, from_limbs, limbs, order_key, quantise, quantise_limbs  # noqa: F401  (the rule's parts)
 
 WORDS = 40
 W_N, W_BAD, W_SUM, W_EXT = 0, 1, 2, 20
@@ -58,38 +58,6 @@ def cell_terms(rho, u, v, E, p, c):
         t = [rho, rho * u, rho * v, rho * E, (0.5 * rho) * q2, p]
         m = np.where(q2 == 0., 0., q2 / (c * c))
     return t, [rho, rho, p, p, e, e, q2, m]
-
-
-def quantise_limbs(t, s):
-    """``quantise`` and ``limbs`` of profile.py on a whole fp64 array → ``(l0, l1, l2, ok)``: the three limbs of |Q| as uint64
-    arrays, ok = False where the value is not finite or |Q| >= 2^95."""
-    t = np.ascontiguousarray(t, dtype=np.float64)
-    b = t.view(np.uint64)
-    one, m32 = np.uint64(1), np.uint64(0xffffffff)
-    ef = ((b >> np.uint64(52)) & np.uint64(0x7ff)).astype(np.int64)
-    frac = b & np.uint64((1 << 52) - 1)
-    m = np.where(ef > 0, frac | np.uint64(1 << 52), frac)
-    sh = np.where(ef > 0, ef, 1) - 1075 - int(s)
-    ok = ef != 0x7ff
-    live = ok & (m != 0)
-    words = np.zeros((5,) + t.shape, dtype=np.uint64)
-    down = live & (sh < 0)
-    r = np.minimum(np.where(down, -sh, 1), 63).astype(np.uint64)      # (a shift by 64 or more rounds to 0, as a shift by 63 does)
-    q, rem, half = m >> r, m & ((one << r) - one), one << (r - one)
-    q = q + ((rem > half) | ((rem == half) & ((q & one) != 0))).astype(np.uint64)
-    words[0] = np.where(down, q & m32, 0)
-    words[1] = np.where(down, q >> np.uint64(32), 0)
-    up = live & (sh >= 0)
-    far = up & (sh >= 95)
-    w, bit = np.where(up & ~far, sh // 32, -1), (np.where(up, sh, 0) % 32).astype(np.uint64)
-    lo, hi = (m & m32) << bit, (m >> np.uint64(32)) << bit               # both below 2^64; their bits do not overlap once placed
-    for k in range(3):
-        sel = w == k
-        words[k] += np.where(sel, lo & m32, 0)
-        words[k + 1] += np.where(sel, (lo >> np.uint64(32)) + (hi & m32), 0)
-        words[k + 2] += np.where(sel, hi >> np.uint64(32), 0)
-    ok = ok & ~far & (words[3] == 0) & (words[4] == 0) & (words[2] < np.uint64(1 << 31))
-    return words[0], words[1], words[2], ok
 
 
 def neutral():

@@ -72,6 +72,38 @@ def limbs(Q):
     return tuple(-v for v in l) if Q < 0 else l
 
 
+def quantise_limbs(t, s):
+    """``quantise`` and ``limbs`` on a whole fp64 array → ``(l0, l1, l2, ok)``: the three limbs of |Q| as uint64
+    arrays, ok = False where the value is not finite or |Q| >= 2^95."""
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    b = t.view(np.uint64)
+    one, m32 = np.uint64(1), np.uint64(0xffffffff)
+    ef = ((b >> np.uint64(52)) & np.uint64(0x7ff)).astype(np.int64)
+    frac = b & np.uint64((1 << 52) - 1)
+    m = np.where(ef > 0, frac | np.uint64(1 << 52), frac)
+    sh = np.where(ef > 0, ef, 1) - 1075 - int(s)
+    ok = ef != 0x7ff
+    live = ok & (m != 0)
+    words = np.zeros((5,) + t.shape, dtype=np.uint64)
+    down = live & (sh < 0)
+    r = np.minimum(np.where(down, -sh, 1), 63).astype(np.uint64)      # (a shift by 64 or more rounds to 0, as a shift by 63 does)
+    q, rem, half = m >> r, m & ((one << r) - one), one << (r - one)
+    q = q + ((rem > half) | ((rem == half) & ((q & one) != 0))).astype(np.uint64)
+    words[0] = np.where(down, q & m32, 0)
+    words[1] = np.where(down, q >> np.uint64(32), 0)
+    up = live & (sh >= 0)
+    far = up & (sh >= 95)
+    w, bit = np.where(up & ~far, sh // 32, -1), (np.where(up, sh, 0) % 32).astype(np.uint64)
+    lo, hi = (m & m32) << bit, (m >> np.uint64(32)) << bit               # both below 2^64; their bits do not overlap once placed
+    for k in range(3):
+        sel = w == k
+        words[k] += np.where(sel, lo & m32, 0)
+        words[k + 1] += np.where(sel, (lo >> np.uint64(32)) + (hi & m32), 0)
+        words[k + 2] += np.where(sel, hi >> np.uint64(32), 0)
+    ok = ok & ~far & (words[3] == 0) & (words[4] == 0) & (words[2] < np.uint64(1 << 31))
+    return words[0], words[1], words[2], ok
+
+
 def from_limbs(l):
     return l[0] + (l[1] << 32) + (l[2] << 64)
 

@@ -141,23 +141,6 @@ def test_reference_for_refuses_what_has_no_solution():
     assert an.reference_for(ArmonParameters(test="Sedov", N=(64, 64), silent=5), 0.5).coord == "r"
 
 
-def test_quantise_array_is_the_scalar_rule():
-    rng = random.Random(20261018)
-    values, scales = [], (-80, -62, -40, -3, 0, 7)
-    for _ in range(4000):
-        values.append(math.ldexp(rng.uniform(-1, 1), rng.randint(-120, 40)))
-    values += [0.0, -0.0, math.inf, -math.inf, math.nan, 5e-324, -5e-324, 0.5, 1.5, 2.5, -2.5, math.ldexp(1.0, 33)]
-    t = np.array(values)
-    for s in scales:
-        a, ok = an.quantise_array(t, s)
-        for i, x in enumerate(values):
-            Q = prof.quantise(x, s)
-            assert bool(ok[i]) == (Q is not None), (x, s)
-            if Q is not None:
-                assert int(a[i]) == abs(Q), (x, s)
-                assert prof.from_limbs(prof.limbs(Q)) == Q and all(abs(l) < 1 << 32 for l in prof.limbs(Q))
-
-
 def random_record(rng):
     raw = an.neutral()
     for k in range(4):

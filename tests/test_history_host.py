@@ -55,19 +55,6 @@ def record_of(rho, u, v, E, scale=(-60,) * 6, **kw):
     return H.reference_record(rho, u, v, E, p, c, scale_exp=scale, **kw)
 
 
-def test_quantise_limbs_is_quantise_and_limbs_of_the_profiles():
-    rng = np.random.default_rng(5)
-    vals = np.concatenate([rng.standard_normal(600) * 10.0 ** rng.integers(-30, 30, 600),
-                           [0.0, -0.0, math.nan, math.inf, -math.inf, 5e-324, 1e308, 2.0 ** 40, -2.0 ** 41 + 1, 0.5, 1.5, 2.5, -2.5]])
-    for s in (-94, -60, -20, 0, 1, 5, -130, -1070, 900):
-        l0, l1, l2, ok = H.quantise_limbs(vals, s)
-        for i, x in enumerate(vals):
-            Q = prof.quantise(x, s)
-            assert (Q is not None) == bool(ok[i]), (x, s)
-            if Q is not None:
-                assert prof.limbs(abs(Q)) == (int(l0[i]), int(l1[i]), int(l2[i])), (x, s)
-
-
 def test_a_nan_cell_counts_in_n_bad_only():
     rho, u, v, E = hand_state()
     clean = record_of(rho, u, v, E)

@@ -121,6 +121,26 @@ def test_quantise_against_exact_rationals():
     assert prof.default_scale([0] * 5) == (-94,) * 5
 
 
+def test_quantise_limbs_is_the_scalar_rule():
+    """The one vectorised quantiser (the oracle of the profile, analytic and history records) against ``quantise`` and ``limbs``,
+    over magnitudes and scales on both sides of the quantum, shifts up to the 2^95 edge included."""
+    rng, nrng = random.Random(20261018), np.random.default_rng(5)
+    values = [math.ldexp(rng.uniform(-1, 1), rng.randint(-120, 40)) for _ in range(4000)]
+    values += (nrng.standard_normal(600) * 10.0 ** nrng.integers(-30, 30, 600)).tolist()
+    values += [0.0, -0.0, math.inf, -math.inf, math.nan, 5e-324, -5e-324, 0.5, 1.5, 2.5, -2.5, math.ldexp(1.0, 33), 1e308, 2.0 ** 40,
+               -2.0 ** 41 + 1]
+    t = np.array(values)
+    for s in (-1070, -130, -94, -80, -62, -60, -40, -20, -3, 0, 1, 5, 7, 900):
+        l0, l1, l2, ok = prof.quantise_limbs(t, s)
+        for i, x in enumerate(values):
+            Q = prof.quantise(x, s)
+            assert bool(ok[i]) == (Q is not None), (x, s)
+            if Q is not None:
+                got = (int(l0[i]), int(l1[i]), int(l2[i]))
+                assert got == prof.limbs(abs(Q)) and prof.from_limbs(got) == abs(Q), (x, s)
+                assert prof.from_limbs(prof.limbs(Q)) == Q and all(abs(l) < 1 << 32 for l in prof.limbs(Q))
+
+
 def test_limbs_round_trip():
     rng = random.Random(7)
     for Q in [0, 1, -1, (1 << 32) - 1, 1 << 32, -(1 << 32), (1 << 64) - 1, 1 << 64, (1 << 95) - 1, -((1 << 95) - 1)] + \
