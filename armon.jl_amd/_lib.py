@@ -195,6 +195,9 @@ SIGNATURES = {
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),
     "armon_hip_state_pack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
     "armon_hip_state_unpack": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dp]),
+    "armon_hip_plane_encode_bound": (C.c_uint64, [_ci, _i64, _i64]),
+    "armon_hip_plane_encode": (_ci, [_vp, _dp, _ci, _i64, _i64, _dp, C.c_uint64, _dp]),
+    "armon_hip_plane_decode": (_ci, [_vp, _dp, C.c_uint64] + [_i64] * 6 + [_dp, _dp]),
     "armon_hip_state_diff_reset": (_ci, [_vp, _ci, _dp]),
     "armon_hip_state_compare": (_ci, [_vp, _i64, _ci, _i64, _i64, _ci, C.POINTER(_dp)] + [_i64] * 6 + [_dp, _dbl, _dbl, _dp, _dp]),
     "armon_hip_profile_reset": (_ci, [_vp, _i64, _dp]),
@@ -255,7 +258,7 @@ def _add_f32_signatures():
     for name in ("perfect_gas_EOS", "bizarrium_EOS", "acoustic", "acoustic_GAD", "cell_update",
                  "advection_first_order", "advection_second_order", "euler_projection", "boundary_conditions",
                  "pack_to_array", "unpack_from_array", "dtCFL_async", "dtCFL", "conservation_vars", "init_test",
-                 "coarsen", "gather_strided", "state_pack", "state_unpack"):
+                 "coarsen", "gather_strided", "state_pack", "state_unpack", "plane_encode", "plane_decode"):
         res, args = SIGNATURES["armon_hip_" + name]
         conv = []
         for a in args:

@@ -15,6 +15,15 @@ copied asynchronously into one of two pinned host buffers, and written at its fi
 Host and staging memory are 2 x band, never a whole field. The band height comes from a byte budget of 256 MB per buffer —
 large enough that a band's kernel and copy (tens of ms) dwarf their launch cost, small enough to be pinned without a thought
 next to a 16384² run (8.6 GB per plane) — or from ``band_rows``. Restore runs the same bands the other way.
+
+PACKED FILES (``compress=True``, the ``checkpoint_compress`` option): file version 2 in the preamble — the header's keys as they
+are (its own ``version`` key included) plus ``codec`` ("xorplane16"), ``index_offset`` and ``index_count``. From ``DATA_OFFSET``
+on come CHUNKS, back to back, 8-byte aligned, in the order they were written: every band of every tile gives one chunk per
+plane, encoded on the device with the lossless codec of csrc/plane_codec.hip (``plane_codec.py`` restates it), or raw (dense
+``[wny][wnx]``) when the encoding is not smaller. At ``index_offset`` sit ``index_count`` records of eight little-endian u64 — plane, codec (0 raw, 1 xorplane16), global
+col0, global row0, wnx, wny, file offset, bytes — and the file ends with them. The digests are those of the values, so they
+are the same in both versions; ``expand`` turns a packed file into the version-1 file of the same state on the host. Loading
+and comparing read a packed file through ``packed_pieces``: saved band by saved band, whatever the reader's decomposition.
 """
 import ctypes as C
 import json
@@ -23,10 +32,16 @@ import struct
 
 import numpy as np
 
+from . import plane_codec
 from ._lib import check, solver_error
 
 MAGIC = b"ARMONCKP"
-VERSION = 1
+VERSION = 1                               # dense planes; what a save without compression writes
+VERSION_PACKED = 2                        # chunks and an index
+CODEC = "xorplane16"
+CODEC_RAW, CODEC_XORPLANE = 0, 1
+INDEX_RECORD = 64                         # eight little-endian u64
+PACKED_KEYS = ("codec", "index_offset", "index_count")
 HEADER_BYTES = 4096                       # the JSON header, padded
 DATA_OFFSET = len(MAGIC) + 4 + 4 + HEADER_BYTES
 BAND_BYTES = 256 << 20                    # per staging / pinned buffer
@@ -77,13 +92,13 @@ def unhex(s):
     return float.fromhex(s)
 
 
-def write_header(f, header):
+def write_header(f, header, version=VERSION):
     """The preamble at offset 0 of the open binary file ``f``: magic, version, header length, padded JSON."""
     text = json.dumps(header, sort_keys=True).encode("utf-8")
     if len(text) > HEADER_BYTES:
         solver_error("io", f"checkpoint header of {len(text)} bytes does not fit in {HEADER_BYTES}")
     f.seek(0)
-    f.write(MAGIC + struct.pack("<II", VERSION, len(text)) + text + b" " * (HEADER_BYTES - len(text)))
+    f.write(MAGIC + struct.pack("<II", version, len(text)) + text + b" " * (HEADER_BYTES - len(text)))
 
 
 def read_header(path):
@@ -97,8 +112,8 @@ def read_header(path):
     if len(pre) < 16 or pre[:8] != MAGIC:
         solver_error("io", f"{path} is not a checkpoint: bad magic {pre[:8]!r}")
     version, length = struct.unpack("<II", pre[8:16])
-    if version != VERSION:
-        solver_error("io", f"{path}: checkpoint version {version}, this build reads version {VERSION}")
+    if version not in (VERSION, VERSION_PACKED):
+        solver_error("io", f"{path}: checkpoint version {version}, this build reads versions {VERSION} and {VERSION_PACKED}")
     if length > HEADER_BYTES or len(pre) < DATA_OFFSET:
         solver_error("io", f"{path}: truncated or damaged header")
     try:
@@ -107,10 +122,24 @@ def read_header(path):
         solver_error("io", f"{path}: unreadable header: {e}")
     _check_header(header, path)
     NX, NY = header["N"]
-    want = DATA_OFFSET + len(header["planes"]) * NX * NY * np.dtype(header["data_type"]).itemsize
+    if version == VERSION_PACKED:
+        at, count = header.get("index_offset"), header.get("index_count")
+        if header.get("codec") != CODEC or not all(isinstance(v, int) and not isinstance(v, bool) for v in (at, count)) \
+                or at < DATA_OFFSET or at % 8 or count < 1:
+            solver_error("io", f"{path}: damaged checkpoint header: codec = {header.get('codec')!r}, index_offset = {at!r}, "
+                               f"index_count = {count!r}")
+        want = at + INDEX_RECORD * count
+    else:
+        if any(k in header for k in PACKED_KEYS):
+            solver_error("io", f"{path}: damaged checkpoint header: a version {VERSION} file with the keys of a packed one")
+        want = DATA_OFFSET + len(header["planes"]) * NX * NY * np.dtype(header["data_type"]).itemsize
     if size != want:
         solver_error("io", f"{path}: truncated checkpoint: {size} bytes, {want} expected")
     return header
+
+
+def is_packed(header):
+    return "index_offset" in header
 
 
 def _is_hexfloat(v):
@@ -324,19 +353,317 @@ def _load_tile(fd, params, grid, names, band_rows):
         pipe.free()
 
 
+# ---- packed files: the index, the reader, the writer ---------------------------------------------------------------------
+def _io(path, what):
+    solver_error("io", f"{path}: {what}")
+
+
+def check_index(path, header, records, mask_table=None):
+    """Validate the index ``records`` (``[count][8]`` integers) of the packed file ``path`` against its header: every record
+    lies inside the chunk area and none overlaps another, windows lie inside the domain, the chunks of each plane tile
+    ``[NY][NX]`` exactly, the planes of a saved band share its window, and the length of every encoded chunk is the one its
+    mask table gives (``mask_table(offset, nbytes)`` → that many bytes of the file; None = not looked at). Any failure is an
+    I/O error that names the file → the saved bands ``[(window, {plane: record})]`` in file order, ``window`` = global
+    ``(col0, row0, wnx, wny)``."""
+    NX, NY = header["N"]
+    item = np.dtype(header["data_type"]).itemsize
+    nplanes, end = len(header["planes"]), header["index_offset"]
+    records = [tuple(int(v) for v in r) for r in records]
+    for rec in records:
+        q, codec, col0, row0, wnx, wny, off, nbytes = rec
+        if q >= nplanes or codec not in (CODEC_RAW, CODEC_XORPLANE):
+            _io(path, f"damaged index: plane {q}, codec {codec}")
+        if wnx < 1 or wny < 1 or col0 + wnx > NX or row0 + wny > NY:
+            _io(path, f"damaged index: the window [{col0}, {col0 + wnx}) x [{row0}, {row0 + wny}) leaves the domain {NX} x {NY}")
+        if off < DATA_OFFSET or off % 8 or off + nbytes > end:
+            _io(path, f"damaged index: a chunk of {nbytes} bytes at offset {off} leaves the chunk area [{DATA_OFFSET}, {end})")
+        if codec == CODEC_RAW and nbytes != wnx * wny * item:
+            _io(path, f"damaged index: a raw chunk of {wnx} x {wny} with {nbytes} bytes")
+        if codec == CODEC_XORPLANE and not 2 * plane_codec.table_bytes(wny, wnx, item) <= nbytes <= plane_codec.bound(wny, wnx, item):
+            _io(path, f"damaged index: an encoded chunk of {wnx} x {wny} with {nbytes} bytes")
+    by_offset = sorted(records, key=lambda r: r[6])
+    for a, b in zip(by_offset, by_offset[1:]):
+        if a[6] + a[7] > b[6]:
+            _io(path, f"damaged index: the chunks at offsets {a[6]} and {b[6]} overlap")
+    for q in range(nplanes):
+        mine = [r for r in records if r[0] == q]
+        xs = sorted({r[2] for r in mine} | {r[2] + r[4] for r in mine} | {0, NX})
+        ys = sorted({r[3] for r in mine} | {r[3] + r[5] for r in mine} | {0, NY})
+        xi, yi = {x: i for i, x in enumerate(xs)}, {y: i for i, y in enumerate(ys)}
+        cover = np.zeros((len(ys) - 1, len(xs) - 1), dtype=np.int64)      # the domain cut at every edge of a window
+        for r in mine:
+            cover[yi[r[3]]:yi[r[3] + r[5]], xi[r[2]]:xi[r[2] + r[4]]] += 1
+        if (cover != 1).any():
+            iy, ix = np.argwhere(cover != 1)[0]
+            _io(path, f"damaged index: the chunks of plane {header['planes'][q]} {'overlap' if cover[iy, ix] else 'leave a hole'} "
+                      f"at cell ({xs[ix]}, {ys[iy]})")
+    bands = {}
+    for rec in by_offset:
+        bands.setdefault(rec[2:6], {})[rec[0]] = rec
+    if any(len(planes) != nplanes for planes in bands.values()):
+        _io(path, "damaged index: the planes of a saved band do not share its window")
+    if mask_table is not None:
+        for q, codec, col0, row0, wnx, wny, off, nbytes in by_offset:
+            if codec == CODEC_XORPLANE:
+                table = plane_codec.table_bytes(wny, wnx, item)
+                masks = np.frombuffer(mask_table(off + table, table), dtype=np.uint8)[:plane_codec.groups(wny, wnx)[1] * item]
+                want = plane_codec.chunk_size(masks.view("<u8" if item == 8 else "<u4"))
+                if want != nbytes:
+                    _io(path, f"damaged chunk at offset {off}: its mask table asks for {want} bytes, the index says {nbytes}")
+    return list(bands.items())
+
+
+def read_index(path, header, fd=None):
+    """The validated saved bands of the packed checkpoint ``path`` (``check_index``), mask tables included."""
+    own = fd is None
+    try:
+        if own:
+            fd = os.open(path, os.O_RDONLY)
+        try:
+            def pread(offset, nbytes):
+                data = os.pread(fd, nbytes, offset)
+                if len(data) != nbytes:
+                    _io(path, f"truncated checkpoint: {len(data)} of {nbytes} bytes at offset {offset}")
+                return data
+            raw = pread(header["index_offset"], INDEX_RECORD * header["index_count"])
+            return check_index(path, header, np.frombuffer(raw, dtype="<u8").reshape(-1, 8), pread)
+        finally:
+            if own:
+                os.close(fd)
+    except OSError as e:
+        solver_error("io", f"cannot read the checkpoint {path}: {e}")
+
+
+def _cut(params, window):
+    """The cells the tile shares with the global ``window`` → global (x0, y0, snx, sny), or None."""
+    ox, oy = params.N_origin[0] - 1, params.N_origin[1] - 1
+    x0, y0 = max(ox, window[0]), max(oy, window[1])
+    x1, y1 = min(ox + params.N[0], window[0] + window[2]), min(oy + params.N[1], window[1] + window[3])
+    return (x0, y0, x1 - x0, y1 - y0) if x1 > x0 and y1 > y0 else None
+
+
+def _readinto(fd, view, offset, path):
+    got = os.preadv(fd, [view], offset)
+    if got != len(view):
+        _io(path, f"truncated checkpoint: {got} of {len(view)} bytes at offset {offset}")
+
+
+def packed_pieces(fd, path, header, bands, params, names, want=None):
+    """THE reader of packed files, for ``load`` and ``compare_state``: for every saved band that intersects this tile (and that
+    ``want(window)`` does not turn down) read the chunks of the planes ``names``, copy them to the device, decode the
+    intersection of each (``armon_hip_plane_decode``; a raw chunk is cut on the host) → yields ``(window, dense)``: the
+    intersection as a window ``(col0, row0, snx, sny)`` of the tile's real cells and the device array ``[len(names)][sny][snx]``
+    that holds it, valid until the next piece is asked for. One piece is in flight at a time."""
+    dev, dtype = params.device, params.data_type
+    item = dtype.itemsize
+    ox, oy = params.N_origin[0] - 1, params.N_origin[1] - 1
+    planes = [header["planes"].index(f) for f in names]
+    work = []
+    for window, recs in bands:
+        cut = _cut(params, window)
+        if cut is not None and (want is None or want((cut[0] - ox, cut[1] - oy, cut[2], cut[3]))):
+            work.append((window, [recs[q] for q in planes], cut))
+    if not work:
+        return
+    chunk_bytes = max(sum(plane_codec.pad8(r[7]) for r in recs if r[1] == CODEC_XORPLANE) for _, recs, _ in work)
+    cells = max(len(names) * cut[2] * cut[3] for _, _, cut in work)
+    bufs = []
+    try:
+        dense, status = dev.empty(cells, dtype), dev.zeros(2, np.uint32)
+        bufs += [dense, status]
+        host = dev.pinned(cells, dtype)
+        bufs.append(host)
+        chunks = chunks_host = None
+        if chunk_bytes:
+            chunks, chunks_host = dev.empty(chunk_bytes, np.uint8), dev.pinned(chunk_bytes, np.uint8)
+            bufs += [chunks, chunks_host]
+        decode = params.fn("plane_decode")
+        for (col0, row0, wnx, wny), recs, (x0, y0, snx, sny) in work:
+            params.wait()                                       # the piece before has left the buffers
+            at = 0
+            for k, (q, codec, _, _, _, _, off, nbytes) in enumerate(recs):
+                if codec == CODEC_RAW:
+                    out = host.array.view(np.uint8)[k * sny * snx * item:(k + 1) * sny * snx * item]
+                    first = off + ((y0 - row0) * wnx + x0 - col0) * item
+                    if snx == wnx:
+                        _readinto(fd, memoryview(out), first, path)
+                    else:
+                        for r in range(sny):
+                            _readinto(fd, memoryview(out[r * snx * item:(r + 1) * snx * item]), first + r * wnx * item, path)
+                    host.copy_to_device_async(dense, n=sny * snx, src_offset=k * sny * snx, dst_offset=k * sny * snx)
+                else:
+                    _readinto(fd, memoryview(chunks_host.array[at:at + nbytes]), off, path)
+                    chunks_host.copy_to_device_async(chunks, n=nbytes, src_offset=at, dst_offset=at)
+                    check(decode(dev.ctx, C.c_void_p(chunks.ptr + at), nbytes, wny, wnx, x0 - col0, y0 - row0, snx, sny,
+                                 C.c_void_p(dense.ptr + k * sny * snx * item), C.c_void_p(status.ptr)))
+                    at += plane_codec.pad8(nbytes)
+            yield (x0 - ox, y0 - oy, snx, sny), dense
+        params.wait()
+        if status.to_host()[0]:
+            _io(path, "damaged chunk: the words of a group end past the chunk")
+    finally:
+        params.wait()
+        for a in bufs:
+            a.free()
+
+
+def _save_tile_packed(fd, params, grid, names, band_rows, offset, records):
+    """Pack, encode, copy and write the bands of one tile as chunks from the file offset ``offset`` on; their index records
+    join ``records`` → (the tile's per-plane digests, the offset after its last chunk). Per band: state_pack into the staging
+    buffer (the digest is that of an unpacked save), plane_encode into a second device buffer; the sizes are read back after
+    the band's event, and only the used bytes — of the encoding, or of the staging buffer where the encoding is not smaller —
+    are copied to pinned memory and written while the next band is packed and encoded. Stream order keeps one buffer of each
+    kind safe: the copies of band k are queued before the kernels of band k + 1."""
+    dev, nx, item = params.device, params.N[0], params.data_type.itemsize
+    ox, oy = params.N_origin[0] - 1, params.N_origin[1] - 1
+    nvars = len(names)
+    rows_max, bands = _bands(params, nvars, band_rows)
+    bound = plane_codec.bound(rows_max, nx, item)
+    encode = params.fn("plane_encode")
+    bufs = []
+    try:
+        digest = dev.zeros(8, np.uint64)
+        bufs.append(digest)
+        stage = dev.empty(nvars * rows_max * nx, params.data_type)
+        bufs.append(stage)
+        enc = dev.empty(nvars * bound, np.uint8)
+        bufs.append(enc)
+        sizes = dev.zeros(8, np.uint64)
+        bufs.append(sizes)
+        sizes_host = dev.pinned(8, np.uint64)
+        bufs.append(sizes_host)
+        host = dev.pinned(nvars * rows_max * nx * item, np.uint8)
+        bufs.append(host)
+
+        def launch(k):
+            r0, rows = bands[k]
+            _move(params, grid, names, (0, r0, nx, rows), stage, digest)
+            check(encode(dev.ctx, C.c_void_p(stage.ptr), nvars, rows, nx, C.c_void_p(enc.ptr), bound, C.c_void_p(sizes.ptr)))
+            sizes_host.copy_from_device_async(sizes, n=nvars)
+            dev.event_record(BAND_EVENT_SLOT)
+
+        def fetch(k):
+            """Queue the copies of band k's used bytes → [(codec, bytes)] per plane."""
+            r0, rows = bands[k]
+            raw = rows * nx * item
+            dev.event_sync(BAND_EVENT_SLOT)
+            out = []
+            for q in range(nvars):
+                n = int(sizes_host.array[q])
+                codec, src = (CODEC_XORPLANE, enc.ptr + q * bound) if n < raw else (CODEC_RAW, stage.ptr + q * raw)
+                n = min(n, raw)
+                check(dev._L.armon_hip_memcpy_async(dev.ctx, C.c_void_p(host.ptr + q * raw), C.c_void_p(src), n, 2))
+                out.append((codec, n))
+            dev.event_record(BAND_EVENT_SLOT + 1)
+            return out
+
+        def flush(k, chunks):
+            nonlocal offset
+            r0, rows = bands[k]
+            raw = rows * nx * item
+            dev.event_sync(BAND_EVENT_SLOT + 1)
+            for q, (codec, n) in enumerate(chunks):
+                _pwrite_all(fd, memoryview(host.array[q * raw:q * raw + n]), offset)
+                records.append((q, codec, ox, oy + r0, nx, rows, offset, n))
+                offset += plane_codec.pad8(n)
+
+        launch(0)
+        for k in range(1, len(bands)):
+            chunks = fetch(k - 1)
+            launch(k)                                   # runs while band k - 1 is written
+            flush(k - 1, chunks)
+        flush(len(bands) - 1, fetch(len(bands) - 1))
+        params.wait()
+        return [int(v) for v in digest.to_host()[:nvars]], offset
+    finally:
+        params.wait()
+        for a in bufs:
+            a.free()
+
+
+def _load_tile_packed(fd, path, header, bands, params, grid, names):
+    """Every saved band that intersects the tile: decode the intersection, one state_unpack of it (the variable index k of
+    the digest is the plane's) → the per-plane digests of what was written into the vectors."""
+    dev = params.device
+    digest = dev.zeros(8, np.uint64)
+    try:
+        for window, dense in packed_pieces(fd, path, header, bands, params, names):
+            _move(params, grid, names, window, dense, digest, unpack=True)
+        params.wait()
+        return [int(v) for v in digest.to_host()[:len(names)]]
+    finally:
+        params.wait()
+        digest.free()
+
+
+def expand(src, dst):
+    """The packed checkpoint ``src`` as the version-1 file ``dst`` of the same state: the same header without the keys of a
+    packed file, the dense planes. Host only (numpy): no device is touched, no digest computed → the header written."""
+    src, dst = str(src), str(dst)
+    header = read_header(src)
+    if not is_packed(header):
+        solver_error("io", f"{src} is not a packed checkpoint")
+    NX, NY = header["N"]
+    dtype = np.dtype(header["data_type"])
+    item = dtype.itemsize
+    plain = {k: v for k, v in header.items() if k not in PACKED_KEYS}
+    tmp = dst + ".tmp"
+    try:
+        fd = os.open(src, os.O_RDONLY)
+        try:
+            bands = read_index(src, header, fd)
+            out = os.open(tmp, os.O_RDWR | os.O_CREAT | os.O_TRUNC, 0o644)
+            try:
+                os.ftruncate(out, DATA_OFFSET + len(header["planes"]) * NX * NY * item)
+                for (col0, row0, wnx, wny), recs in bands:
+                    for q, codec, _, _, _, _, off, nbytes in recs.values():
+                        data = os.pread(fd, nbytes, off)
+                        if len(data) != nbytes:
+                            _io(src, f"truncated checkpoint: {len(data)} of {nbytes} bytes at offset {off}")
+                        try:
+                            plane = (plane_codec.decode_reference(data, wny, wnx, dtype) if codec == CODEC_XORPLANE
+                                     else np.frombuffer(data, dtype=dtype).reshape(wny, wnx))
+                        except ValueError as e:
+                            _io(src, f"damaged chunk at offset {off}: {e}")
+                        first = DATA_OFFSET + ((q * NY + row0) * NX + col0) * item
+                        if wnx == NX:
+                            _pwrite_all(out, plane.tobytes(), first)
+                        else:
+                            for r in range(wny):
+                                _pwrite_all(out, plane[r].tobytes(), first + r * NX * item)
+                with os.fdopen(os.dup(out), "r+b") as f:
+                    write_header(f, plain)
+                    f.flush()
+                os.fsync(out)
+            finally:
+                os.close(out)
+        finally:
+            os.close(fd)
+        os.replace(tmp, dst)
+    except BaseException as e:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+        if isinstance(e, OSError):
+            solver_error("io", f"cannot expand the checkpoint {src} into {dst}: {e}")
+        raise
+    return plain
+
+
 # ---- a whole run ---------------------------------------------------------------------------------------------------------
 def _refuse_ranks(params):
     if params.use_MPI:
         solver_error("config", "checkpoint / restart is not supported for ranks of a process group (use_MPI=true)")
 
 
-def save(tiles, gdt, readback, path, band_rows=None):
+def save(tiles, gdt, readback, path, band_rows=None, compress=None):
     """Write the checkpoint ``path`` of the run whose tiles are the ``(params, grid)`` of ``tiles`` (idle, nothing in flight
     between them), at the boundary before cycle ``gdt.cycle`` → the header. ``readback`` = the run's ``DtReadback``: the CFL
     step the previous cycle left in flight (fused path) is taken, stored, and primed again exactly as a restart primes it, so
-    that writing a checkpoint cannot change the run's bits. Written as ``path.tmp``, then renamed."""
+    that writing a checkpoint cannot change the run's bits. Written as ``path.tmp``, then renamed. ``compress``: write a packed
+    file (None = the ``checkpoint_compress`` option); without it the file is version 1, byte for byte what it always was."""
     p0 = tiles[0][0]
     _refuse_ranks(p0)
+    compress = bool(getattr(p0, "checkpoint_compress", False) if compress is None else compress)
     names = plane_names(p0)
     pending = None
     if (gdt.cycle - 1) in readback.inflight:
@@ -359,12 +686,21 @@ def save(tiles, gdt, readback, path, band_rows=None):
     except OSError as e:
         solver_error("io", f"cannot create the checkpoint {path}: {e}")
     try:
-        os.ftruncate(fd, DATA_OFFSET + len(names) * NX * NY * p0.data_type.itemsize)
-        for params, grid in tiles:
-            total = [(t + d) & MASK for t, d in zip(total, _save_tile(fd, params, grid, names, band_rows))]
+        if compress:
+            offset, records = DATA_OFFSET, []
+            for params, grid in tiles:
+                digests, offset = _save_tile_packed(fd, params, grid, names, band_rows, offset, records)
+                total = [(t + d) & MASK for t, d in zip(total, digests)]
+            _pwrite_all(fd, np.array(records, dtype="<u8").tobytes(), offset)
+            os.ftruncate(fd, offset + INDEX_RECORD * len(records))
+            header.update(codec=CODEC, index_offset=offset, index_count=len(records))
+        else:
+            os.ftruncate(fd, DATA_OFFSET + len(names) * NX * NY * p0.data_type.itemsize)
+            for params, grid in tiles:
+                total = [(t + d) & MASK for t, d in zip(total, _save_tile(fd, params, grid, names, band_rows))]
         header["digests"] = {f: f"{d:016x}" for f, d in zip(names, total)}
         with os.fdopen(os.dup(fd), "r+b") as f:
-            write_header(f, header)
+            write_header(f, header, VERSION_PACKED if compress else VERSION)
             f.flush()
         os.fsync(fd)
         os.close(fd)
@@ -396,8 +732,11 @@ def load(tiles, gdt, readback, path, band_rows=None):
     try:
         fd = os.open(path, os.O_RDONLY)
         try:
+            bands = read_index(path, header, fd) if is_packed(header) else None     # validated before anything goes to a device
             for params, grid in tiles:
-                total = [(t + d) & MASK for t, d in zip(total, _load_tile(fd, params, grid, names, band_rows))]
+                digests = (_load_tile(fd, params, grid, names, band_rows) if bands is None
+                           else _load_tile_packed(fd, str(path), header, bands, params, grid, names))
+                total = [(t + d) & MASK for t, d in zip(total, digests)]
         finally:
             os.close(fd)
     except OSError as e:

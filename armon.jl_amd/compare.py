@@ -1,6 +1,7 @@
 """State comparison on the device (csrc/state_compare.hip): what separates the state of a run from a checkpoint, or from the
 state of another run, reduced where the state lives to one 64-byte record per variable. No reference counterpart: the
-reference compares text files on the host (ref src/io.jl:113-227; ``io.compare_host`` keeps that path as it is).
+reference compares text files on the host (ref src/io.jl:113-227; ``io.compare_host`` keeps that path as it is). A packed checkpoint (checkpoint.py, file version 2) is read through the
+reader ``load_state`` uses, saved band by saved band, and gives the records of the unpacked file of the same state.
 
 PER CELL, ``a`` = our value, ``b`` = the reference's, all arithmetic in the data type:
 
@@ -299,6 +300,51 @@ def _read_band(fd, params, header, names, pipe, s, r0, rows):
     pipe.host[s].copy_to_device_async(pipe.stage[s], n=len(names) * rows * nx)
 
 
+def _tile_against_packed(fd, path, header, packed, params, grid, names, rtol, atol):
+    """A packed file: the saved bands that intersect this tile, decoded by the reader ``load_state`` uses
+    (checkpoint.packed_pieces), each compared where it lands and merged on the device → the tile's records."""
+    dev = params.device
+    diff = dev.empty(64, np.uint64)
+    try:
+        _reset(params, diff, len(names))
+        for window, dense in checkpoint.packed_pieces(fd, path, header, packed, params, names):
+            _compare_window(params, grid, names, window, dense.ptr, rtol, atol, diff)
+        return _records(params, diff, len(names))
+    finally:
+        params.wait()
+        diff.free()
+
+
+def _list_against_packed(fd, path, header, packed, params, grid, names, rtol, atol, lister):
+    """The second pass over a packed file: only the saved bands that can still add to the listing are decoded again; the
+    reference's rows come from the decoded band on the device."""
+    dev, nvars, item = params.device, len(names), params.data_type.itemsize
+    diff = row_out = None
+    try:
+        diff = dev.empty(64, np.uint64)
+        for window, dense in checkpoint.packed_pieces(fd, path, header, packed, params, names, want=lister.wants):
+            if not lister.wants(window):
+                continue                                            # (the pieces before this one may have filled the listing)
+            wnx, rows = window[2], window[3]
+            if row_out is None or len(row_out) < nvars * rows:
+                if row_out is not None:
+                    params.wait()
+                    row_out.free()
+                row_out = dev.empty(nvars * rows, np.uint32)
+            row_out.fill_bytes(0)
+            _reset(params, diff, nvars)
+            _compare_window(params, grid, names, window, dense.ptr, rtol, atol, diff, row_out)
+            if any(r[2] for r in _records(params, diff, nvars)):
+                counts = row_out.to_host()[:nvars * rows].reshape(nvars, rows)
+                lister.band(window, counts,
+                            lambda q, r: _d2h(dev, dense.ptr + ((q * rows + r) * wnx) * item, wnx, params.data_type))
+    finally:
+        params.wait()
+        for a in (diff, row_out):
+            if a is not None:
+                a.free()
+
+
 def _tile_against_file(fd, header, params, grid, names, rtol, atol, band_rows):
     """Stream this tile's window of the file's planes through the pipeline (checkpoint._load_tile's direction) into
     state_compare → the tile's records. The bands merge on the device; the host waits for a buffer, never for a result."""
@@ -525,11 +571,16 @@ def compare_state(tiles, ref, rtol=None, atol=0.0, names=None, limit=20, band_ro
         solver_error("config", f"the checkpoint {ref} holds the planes {theirs}, not all of {names}")
     lister = _Lister(names, rtol, atol, limit) if limit > 0 else None
     try:
+        packed = None
         if header is not None:
             fd = os.open(ref, os.O_RDONLY)
+            if checkpoint.is_packed(header):                        # chunks and an index: validated, then read band by saved band
+                packed = checkpoint.read_index(ref, header, fd)
         total = [NEUTRAL] * len(names)
         for params, grid in tiles:
-            if header is not None:
+            if packed is not None:
+                records = _tile_against_packed(fd, ref, header, packed, params, grid, names, rtol, atol)
+            elif header is not None:
                 records = _tile_against_file(fd, header, params, grid, names, rtol, atol, band_rows)
             else:
                 records = _tile_against_tiles(params, grid, others, names, rtol, atol, band_rows)
@@ -539,7 +590,9 @@ def compare_state(tiles, ref, rtol=None, atol=0.0, names=None, limit=20, band_ro
             lister.tile(params, grid, records)
             if not lister.wants((0, 0, params.N[0], params.N[1])):
                 continue                                            # every cell of this tile comes after the ones held
-            if header is not None:
+            if packed is not None:
+                _list_against_packed(fd, ref, header, packed, params, grid, names, rtol, atol, lister)
+            elif header is not None:
                 _list_against_file(fd, header, params, grid, names, rtol, atol, band_rows, lister)
             else:
                 _list_against_tiles(params, grid, others, names, rtol, atol, band_rows, lister)

@@ -412,10 +412,10 @@ class TileGroup(NativeGroup):
         from . import checkpoint
         return checkpoint.state_digest(self._tiles_at_rest(), tuple(names))
 
-    def save_state(self, path, band_rows=None):
+    def save_state(self, path, band_rows=None, compress=None):
         """Each tile writes its window of the GLOBAL planes: the file is byte-identical to the single block's."""
         from . import checkpoint
-        return checkpoint.save(self._tiles_at_rest(), self.global_dt, self.dt, path, band_rows=band_rows)
+        return checkpoint.save(self._tiles_at_rest(), self.global_dt, self.dt, path, band_rows=band_rows, compress=compress)
 
     def load_state(self, path, band_rows=None):
         from . import checkpoint

@@ -223,10 +223,13 @@ class ArmonParameters:
                      error_norms_step=0, error_norms_at_end=False, error_norms_samples=1, error_norms_file="error_norms",
                      start_from_exact=None, history_step=0, history_file="history", history_gauges=(), history_capacity=256,
                      history_scale_exp=None, image_step=0, image_at_end=False, image_quantity="grad_rho", image_reduce=None,
-                     image_coarsen=None, image_transfer=None, image_range=None, image_file="image", **options):
+                     image_coarsen=None, image_transfer=None, image_range=None, image_file="image", checkpoint_compress=False,
+                     **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
-        ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart).
+        ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart);
+        ``checkpoint_compress``: checkpoints are written packed — file version 2, every band of every plane encoded on the
+        device with a lossless codec (csrc/plane_codec.hip) — instead of as dense planes; reading takes either.
         ``compare_step=k``: after every k completed cycles (0 = off) the state is compared on the device with
         ``<compare_dir>/<compare_file>_<cycle:06d>.ckpt`` — the checkpoints of a reference run — within ``comparison_tolerance``
         (relative) and ``comparison_atol`` (a number, or a dict plane → number); the file's time is compared with the run's
@@ -268,6 +271,9 @@ class ArmonParameters:
         if not self.checkpoint_file or "/" in self.checkpoint_file:
             solver_error("config", f"checkpoint_file is a file name inside output_dir, got {checkpoint_file!r}")
         self.checkpoint_at_end = bool(checkpoint_at_end)
+        if not isinstance(checkpoint_compress, (bool, np.bool_)):
+            solver_error("config", f"checkpoint_compress must be true or false, got {checkpoint_compress!r}")
+        self.checkpoint_compress = bool(checkpoint_compress)
         self.restart_from = None if restart_from is None else str(restart_from)
         if self.restart_from is not None and (self.compare or self.is_ref):
             solver_error("config", "restart_from cannot be combined with compare / is_ref: the step files of a reference "

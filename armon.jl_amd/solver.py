@@ -381,10 +381,10 @@ class BlockGrid:
         from . import checkpoint
         return checkpoint.state_digest([(self.params, self)], tuple(names))
 
-    def save_state(self, path, band_rows=None):
+    def save_state(self, path, band_rows=None, compress=None):
         """Write a checkpoint of this block (checkpoint.py) → its header."""
         from . import checkpoint
-        return checkpoint.save([(self.params, self)], self.global_dt, self.dt, path, band_rows=band_rows)
+        return checkpoint.save([(self.params, self)], self.global_dt, self.dt, path, band_rows=band_rows, compress=compress)
 
     def load_state(self, path, band_rows=None):
         """Load the state, the clock and the pending CFL step of a checkpoint over this (initialised) block → its header."""

@@ -312,6 +312,32 @@ ARMON_API int armon_hip_state_unpack(armon_ctx*, int64_t row_length, int nghost,
         double* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
         int64_t global_nx, const double* dense_dev, uint64_t* digest_dev);
 
+/* ---- lossless plane codec "xorplane16" of packed checkpoints (no reference counterpart; csrc/plane_codec.hip) ---- */
+/* A CHUNK encodes one dense plane of `rows` x `wnx` elements of W = 64 or 32 bits, row-major; u[r][c] = the bit pattern.
+ *   t[r][c] = u[r][c] if r % 16 == 0, else u[r][c] ^ u[r-1][c]                    (row blocks of 16 rows from the first row)
+ *   a row is cut into G = ceil(wnx / 64) groups of 64 columns; group g = r G + j, n = rows G; lane l = column 64 j + l
+ *   base = t[r][64 j]; res[0] = 0; res[l] = t[r][64 j + l] ^ t[r][64 j + l - 1] inside the plane, 0 past it
+ *   mask = OR of res over the lanes; per set bit k of mask, ascending, one 64-bit word whose bit l is bit k of res[l]
+ * Chunk bytes, little-endian: base[n] (W/8 bytes each, zero-padded to a multiple of 8), mask[n] (the same), then the words
+ * of group 0, 1, ... back to back: 2 pad8(n W / 8) + 8 sum popcount(mask) bytes, a function of the values and the shape only.
+ * armon_hip_plane_encode_bound: the largest chunk of that shape, 2 pad8(n W / 8) + 8 W n (0 for an invalid shape or width).
+ * armon_hip_plane_encode: `dense_dev` = [nplanes][rows][wnx], nplanes <= 8; the chunk of plane q lands at
+ * `out_dev + q * plane_capacity` (device, 8-byte aligned), its size in `sizes_dev[q]` (device); no byte past that size is
+ * written. `plane_capacity` must be a multiple of 8 and at least the bound.
+ * armon_hip_plane_decode: the sub-window [col0, col0 + snx) x [row0, row0 + sny) of the chunk at `chunk_dev` (device, 8-byte
+ * aligned, `chunk_bytes` long) into the dense `out_dev` = [sny][snx]. Nothing past `chunk_bytes` is read: a group whose words
+ * would end beyond it decodes as if it had none and sets `*status_dev` (device, cleared by the caller) to 1. Whether a chunk
+ * is consistent is the host's to check before it gets here (plane_codec.check_chunk).
+ * Both are async on the context's stream, use no atomics, and keep the offsets of the groups (n 64-bit words per plane, plus
+ * one per 2048) in the context's reduction scratch, which grows as in armon_hip_state_pack: one stream synchronisation, refused
+ * inside a capture or while a captured graph is alive. Refused (ARMON_ERR_INVALID_ARG, before any launch): a NULL context or
+ * pointer, non-positive sizes, a capacity below the bound, a sub-window that leaves the chunk, `chunk_bytes` below the tables. */
+ARMON_API uint64_t armon_hip_plane_encode_bound(int elem_bytes, int64_t rows, int64_t wnx);
+ARMON_API int armon_hip_plane_encode(armon_ctx*, const double* dense_dev, int nplanes, int64_t rows, int64_t wnx,
+        void* out_dev, uint64_t plane_capacity, uint64_t* sizes_dev);
+ARMON_API int armon_hip_plane_decode(armon_ctx*, const void* chunk_dev, uint64_t chunk_bytes, int64_t rows, int64_t wnx,
+        int64_t col0, int64_t row0, int64_t snx, int64_t sny, double* out_dev, uint32_t* status_dev);
+
 /* ---- state comparison on the device (no reference counterpart; csrc/state_compare.hip) ---- */
 /* What separates two states, per variable: 64 bytes, every field MERGES (counts add, first_out is a minimum, a (value, position)
  * pair takes the larger bit pattern and on equal patterns the smaller position), so the record of a domain is the merge of
@@ -631,6 +657,10 @@ ARMON_API int armon_hip_state_pack_f32(armon_ctx*, int64_t row_length, int nghos
 ARMON_API int armon_hip_state_unpack_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, int nvars,
         float* const* vars, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_first,
         int64_t global_nx, const float* dense_dev, uint64_t* digest_dev);
+ARMON_API int armon_hip_plane_encode_f32(armon_ctx*, const float* dense_dev, int nplanes, int64_t rows, int64_t wnx,
+        void* out_dev, uint64_t plane_capacity, uint64_t* sizes_dev);
+ARMON_API int armon_hip_plane_decode_f32(armon_ctx*, const void* chunk_dev, uint64_t chunk_bytes, int64_t rows, int64_t wnx,
+        int64_t col0, int64_t row0, int64_t snx, int64_t sny, float* out_dev, uint32_t* status_dev);
 
 /* ---- fused sweep: EOS → BC (in-tile mirror) → fluxes → cell update → advection → projection ---- */
 /* One call = one directional sweep of solver_cycle (ref src/solver.jl:300-316) over one block, reading
