@@ -17,6 +17,12 @@ OUT = os.path.join(HERE, "libarmon_hip.so")
 OUT_ALT = os.path.join(HERE, "libarmon_hip_alt.so")
 ALT_SOURCES = ("fused_sweep_f64.hip", "fused_sweep_f32.hip")     # the translation units the define changes
 ALT_FLAGS = ["-DARMON_ALT_KERNELS"]
+# Test infrastructure, not product: one elementwise kernel per arithmetic primitive of csrc/physics.hpp (xct::) and
+# csrc/sweep_pipeline.hpp (fused::fast::), compiled with the product's own flags so that what
+# tests/test_gpu_arith_primitives.py drives is what the sweeps compile. A library of its own: the exports of the two above
+# stay what include/armon_hip.h declares.
+OUT_PROBE = os.path.join(HERE, "libarmon_arith_probe.so")
+PROBE_SOURCE = os.path.join(HERE, "..", "tests", "native", "arith_probe.hip")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 # -ffp-contract=off: the "exact" kernels must evaluate one IEEE op per source op (bit parity with the
@@ -43,9 +49,13 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force=False, verbose=False, alt=True):
+def build(force=False, verbose=False, alt=True, probe=True):
     objs, objs_alt, jobs = [], [], []
     hdrs = headers()
+    probe_jobs = []                                        # one translation unit, compiled and linked in one command
+    if probe and (force or _stale(OUT_PROBE, [PROBE_SOURCE] + hdrs + [__file__])):
+        probe_jobs.append([HIPCC, *CXXFLAGS, "-shared", PROBE_SOURCE, "-o", OUT_PROBE, "-Wl,-rpath,/opt/rocm/lib",
+                           "-Wl,--no-undefined"])
     os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for src in sources():
         obj = os.path.join(HERE, "build", src[:-4] + ".o")
@@ -69,7 +79,7 @@ def build(force=False, verbose=False, alt=True):
             print(r.stderr)
 
     with ThreadPoolExecutor(max_workers=4) as ex:
-        list(ex.map(run, jobs))
+        list(ex.map(run, jobs + probe_jobs))
     for out, group in ((OUT, objs),) + (((OUT_ALT, objs_alt),) if alt else ()):
         if jobs or force or _stale(out, group):
             run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, *group,

@@ -18,9 +18,11 @@ namespace armon {
 // ======================================================================================================
 // The compiler's IEEE a/b is v_div_scale ×2, v_rcp_f64, two Newton steps, quotient, remainder, v_div_fmas,
 // v_div_fixup: 11 instructions, 20 times per cell. The scale / fix-up instructions only act when an operand or
-// the quotient leaves ~2^±500 (or is 0, inf, NaN); everything the solver divides is within 1e±30, and there the
-// remaining operations — reproduced below in the same order — give the same, correctly rounded bits (asserted by
-// every bit-parity test against the oracle, which divides with the CPU's IEEE instruction). A prepared denominator
+// the quotient leaves a wide middle range (or is 0, inf, NaN); everything the solver divides is within 1e±30, and there the
+// remaining operations — reproduced below in the same order — give the same, correctly rounded bits. Asserted operand by
+// operand on [1e-30, 1e30] by tests/test_gpu_arith_primitives.py (random operands, binade edges, zero remainders, zeros of
+// both signs, quotients 1 ... 8 parts in 2^53 from a tie; quo_t down through the subnormal range); measured, not asserted,
+// by the same file: with operands and quotient anywhere in 2^±450, 4e5 pairs, not a bit differs. A prepared denominator
 // (reciprocal refined once: 5 instructions) then serves every quotient that shares it for 3 instructions each:
 // the two Godunov quotients (ref src/riemann_schemes.jl:27-28), the three u,v,E of the projection, its four /dx,
 // the two dt/dm of the cell update, consecutive slope ratios.
@@ -64,7 +66,9 @@ template <> struct Den<double> {
     {
         const double q = a * r;
         const double rem = __builtin_fma(-b, q, a);
-        return __builtin_fma(rem, r, q);
+        // A zero numerator: q already is IEEE's zero, sign included, while the refinement turns -0 / b (b > 0) into
+        // (+0) r + (-0) = +0. The transverse velocity of a fluid at rest can be -0, and the oracle keeps it.
+        return (a == 0.) ? q : __builtin_fma(rem, r, q);
     }
     // a / b where the quotient may fall below the normal range — the velocities of a fluid at rest, their fluxes and slope
     // ratios (Sedov's far field carries 1e-320). There quo()'s remainder step underflows and the result can be one unit of
@@ -77,7 +81,11 @@ template <> struct Den<double> {
         const double q = quo(a);
 #ifndef ARMON_LOOSE_SUBNORMAL
         // (an exact zero — the transverse velocity of Sod, a fluid at rest — is the same zero either way and stays on the fast path)
-        if (__builtin_expect(__builtin_fabs(q) < 0x1p-960 && a != 0., 0)) return a / b;
+        // The remainder a - b q is a multiple of ulp(b) ulp(q) ~ 2^-104 |a|: it is exact, and the result IEEE's, only while
+        // that stays on the subnormal grid, |a| >= ~2^-969. A tiny numerator over a small denominator (a slope ratio's
+        // 1e-6) gives a quotient ABOVE 2^-960 with an inexact remainder, so the numerator is guarded as well as the quotient
+        // (tests/test_gpu_arith_primitives.py: one quotient in 200 of that set was one ulp off with the quotient alone).
+        if (__builtin_expect((__builtin_fabs(q) < 0x1p-960 || __builtin_fabs(a) < 0x1p-960) && a != 0., 0)) return a / b;
 #endif
         return q;
     }
