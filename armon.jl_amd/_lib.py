@@ -122,6 +122,18 @@ class DeriveSpec(C.Structure):
                 ("neighbours", C.c_int32), ("gamma", C.c_double), ("dx", C.c_double), ("dy", C.c_double)]
 
 
+class Region(C.Structure):
+    """armon_region — one region of a user-defined initial state (include/armon_hip.h, armon_hip_init_regions)."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("a", C.c_double * 4),
+                ("rho", C.c_double), ("u", C.c_double), ("v", C.c_double), ("E", C.c_double)]
+
+
+class RegionF32(C.Structure):
+    """armon_region_f32."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("a", C.c_float * 4),
+                ("rho", C.c_float), ("u", C.c_float), ("v", C.c_float), ("E", C.c_float)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -190,6 +202,11 @@ SIGNATURES = {
     "armon_hip_init_test": (_ci, [_vp, Range, _ci, _i64, _i64, _ci, C.POINTER(_i64 * 2),
                                   C.POINTER(_i64 * 2), C.POINTER(_dbl * 2), C.POINTER(_dbl * 2),
                                   _dbl, C.POINTER(BlockDataPtrs)]),
+    "armon_hip_init_regions": (_ci, [_vp, Range, _i64, _ci, C.POINTER(_i64 * 2), C.POINTER(_dbl * 2), C.POINTER(_dbl * 2), _ci,
+                                     C.POINTER(_dbl * 4), _ci, C.POINTER(Region)] + [_dp] * 4),
+    "armon_hip_init_regions_f32": (_ci, [_vp, Range, _i64, _ci, C.POINTER(_i64 * 2), C.POINTER(C.c_float * 2),
+                                         C.POINTER(C.c_float * 2), _ci, C.POINTER(C.c_float * 4), _ci, C.POINTER(RegionF32)]
+                                   + [_dp] * 4),
     "armon_hip_coarsen": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 6),
     "armon_hip_derive": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 4 + [C.POINTER(DeriveSpec), _dp]),
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),

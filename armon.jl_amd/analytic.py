@@ -31,6 +31,14 @@ W_N, W_BAD, W_D, W_ABS, W_SQ, W_MAX, W_AT = 0, 1, 2, 5, 8, 11, 12
 NO_CLOSED_FORM = ("Sod_circ", "Bizarrium", "DebugIndexes")
 
 
+def has_closed_form(test):
+    """Whether ``reference_for`` knows the exact solution of ``test``: a built-in case by its name; a user-defined problem
+    (problem.py) when it is a one-dimensional perfect-gas Riemann problem at gamma = 7/5 (``BoundProblem.riemann_setup``)."""
+    if getattr(test, "is_problem", False):
+        return test.riemann_setup() is not None
+    return test.name not in NO_CLOSED_FORM
+
+
 # ---- the Riemann problem ---------------------------------------------------------------------------------------------------
 def riemann_exact(left, right, gamma=7 / 5, tol=1e-15, max_iter=100):
     """The exact solution of the perfect-gas Riemann problem between ``left`` and ``right`` = (rho, u, p): Newton iteration on
@@ -236,7 +244,7 @@ def reference_for(params, time, nodes=4000):
     """The exact solution of the run's test case at ``time`` → ``ExactSolution``. Refused (``SolverException("analytic", …)``):
     a case without a closed form, a time <= 0, and a time at which a wave has reached a wall."""
     name = params.test.name
-    if name in NO_CLOSED_FORM:
+    if not has_closed_form(params.test):
         solver_error("analytic", f"the test case {name} has no closed-form solution (give error_norms a table: ExactSolution.table)")
     time = float(time)
     if not (math.isfinite(time) and time > 0):
@@ -244,13 +252,19 @@ def reference_for(params, time, nodes=4000):
     gamma = float(params.test.gamma)
     ox, oy = (float(o) for o in params.origin)
     lx, ly = (float(d) for d in params.domain_size)
-    if name in ("Sod", "Sod_y"):
-        r = riemann_exact((1.0, 0.0, (gamma - 1) * 1.0 * 2.5), (0.125, 0.0, (gamma - 1) * 0.125 * 2.0), gamma)
-        lo, length, x0 = (ox, lx, 0.5) if name == "Sod" else (oy, ly, 0.5)
+    setup = None
+    if getattr(params.test, "is_problem", False):
+        setup = params.test.riemann_setup()         # a user-defined problem: decided by what it holds, never by its name
+    elif name in ("Sod", "Sod_y"):
+        setup = ("x" if name == "Sod" else "y", 0.5, (1.0, 0.0, (gamma - 1) * 1.0 * 2.5), (0.125, 0.0, (gamma - 1) * 0.125 * 2.0))
+    if setup is not None:
+        axis, x0, left, right = setup
+        r = riemann_exact(left, right, gamma)
+        lo, length = (ox, lx) if axis == "x" else (oy, ly)
         if x0 + r.speeds[0] * time <= lo or x0 + r.speeds[4] * time >= lo + length:
             solver_error("analytic", f"at t = {time:.6g} a wave of the {name} problem has reached a wall (speeds {r.speeds[0]:.5f}, "
                                      f"{r.speeds[4]:.5f} from {x0}): the solution of the unbounded problem no longer applies")
-        return ExactSolution(RIEMANN, "x" if name == "Sod" else "y", (x0, 0.0) if name == "Sod" else (0.0, x0), gamma, time=time, riemann=r)
+        return ExactSolution(RIEMANN, axis, (x0, 0.0) if axis == "x" else (0.0, x0), gamma, time=time, riemann=r)
     if name == "Sedov":
         E0, count = sedov_energy(params)
         rho0, p0 = 1.0, (gamma - 1) * 1.0 * 2.5e-14

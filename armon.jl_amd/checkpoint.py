@@ -52,6 +52,9 @@ MASK = (1 << 64) - 1
 # every option that decides bits: a restart must agree with the file on all of them
 BIT_FIELDS = ("data_type", "N", "test", "domain_size", "origin", "periodic", "scheme", "riemann_limiter", "projection", "axis_splitting",
               "eos", "cfl", "cst_dt", "Dt", "use_fused_sweep", "exact_arithmetic")
+# only in the header of a user-defined problem (problem.py; "test" is then "Problem:<name>"): gamma as a hexfloat and the
+# sha256 of the problem's canonical description
+PROBLEM_FIELDS = ("gamma", "problem_digest")
 
 
 # ---- digest (host restatement: tests, and files checked without a device) ------------------------------------------------
@@ -180,22 +183,26 @@ def _check_header(header, path):
 def bit_options(params):
     """What decides the bits of a run, as the header stores it (floats as hex text)."""
     fused = bool(params.use_fused_sweep)
-    return {"data_type": params.data_type.name, "N": list(params.global_grid),
-            "domain_size": [hexfloat(v) for v in params.domain_size], "origin": [hexfloat(v) for v in params.origin],
-            "periodic": [bool(v) for v in params.periodic], "test": params.test.name, "scheme": params.riemann_scheme, "riemann_limiter": params.riemann_limiter,
-            "projection": params.projection_scheme, "axis_splitting": params.axis_splitting, "eos": params.test.eos,
-            "cfl": hexfloat(params.cfl), "cst_dt": bool(params.cst_dt), "Dt": hexfloat(params.Dt),
-            "use_fused_sweep": fused, "exact_arithmetic": bool(params.exact_arithmetic) if fused else None}
+    test = params.test
+    options = {"data_type": params.data_type.name, "N": list(params.global_grid),
+               "domain_size": [hexfloat(v) for v in params.domain_size], "origin": [hexfloat(v) for v in params.origin],
+               "periodic": [bool(v) for v in params.periodic], "test": getattr(test, "header_name", test.name), "scheme": params.riemann_scheme, "riemann_limiter": params.riemann_limiter,
+               "projection": params.projection_scheme, "axis_splitting": params.axis_splitting, "eos": test.eos,
+               "cfl": hexfloat(params.cfl), "cst_dt": bool(params.cst_dt), "Dt": hexfloat(params.Dt),
+               "use_fused_sweep": fused, "exact_arithmetic": bool(params.exact_arithmetic) if fused else None}
+    if getattr(test, "is_problem", False):      # a user-defined problem (problem.py): the headers of the built-in cases are untouched
+        options.update(gamma=hexfloat(test.gamma), problem_digest=test.digest)
+    return options
 
 
 def check_compatible(params, header, path):
     """A configuration error that names the first bit-deciding field on which the file and the run disagree, or a file that
     leaves nothing to run. ``nghost``, the decomposition, ``maxcycle``, ``maxtime`` and the output options are free."""
     mine = bit_options(params)
-    for k in BIT_FIELDS:
-        if header.get(k) != mine[k]:
+    for k in BIT_FIELDS + PROBLEM_FIELDS:
+        if header.get(k) != mine.get(k):
             solver_error("config", f"the checkpoint {path} was written with {k} = {header.get(k)!r}, this run has "
-                                   f"{k} = {mine[k]!r}")
+                                   f"{k} = {mine.get(k)!r}")
     if header["cycle"] >= params.maxcycle or params.T(unhex(header["time"])) >= params.T(params.maxtime):
         solver_error("config", f"the checkpoint {path} is at cycle {header['cycle']}, time {unhex(header['time'])}: nothing left "
                                f"to run with maxcycle = {params.maxcycle}, maxtime = {params.maxtime}")

@@ -7,16 +7,12 @@
 // reference's 1-D ndrange + divrem (ref src/generic_kernel.jl:784-791).
 #include "common.hpp"
 #include "physics.hpp"
+#include "range_walk.hpp"
 #include "sweep_spatial.hpp"   // wavefront shifts (from_prev_lane / from_next_lane)
 
 using namespace armon;
 
 namespace {
-
-__device__ __forceinline__ int64_t row_base(const armon_range& r, int64_t j)
-{
-    return r.col_start + j * r.col_step + r.row_start;
-}
 
 // Outputs that the next kernel re-reads only after 2+ GB of other traffic (fluxes, advected quantities): streaming
 // stores, so that they do not displace the neighbour rows the stencils DO re-read from L2.
@@ -29,20 +25,7 @@ template <typename T> __device__ __forceinline__ void st_stream(T* p, T v)
 #endif
 }
 
-// Threads are laid along a row of the range, shifted left so that every wave's row segment starts on a 64-B sector
-// of the array (ranges start g or g-w cells into a row: without the shift each 512-B segment straddles one more sector;
-// the fused sweeps gained 9-11 % from the same alignment). Grids are sized for row_len + 15 threads.
-template <typename T> __device__ __forceinline__ int64_t row_thread(const armon_range& r)
-{
-    constexpr int64_t per_sector = 64 / sizeof(T);
-    return (int64_t)blockIdx.x * blockDim.x + threadIdx.x - ((r.col_start + r.row_start) & (per_sector - 1));
-}
-
-#define ARMON_FOR_RANGE(r, i)                                                         \
-    const int64_t k_ = row_thread<T>(r);                                               \
-    if (k_ >= 0 && k_ < (r).row_len)                                                   \
-        for (int64_t j_ = blockIdx.y, i = row_base((r), j_) + k_; j_ < (r).col_len;    \
-             j_ += gridDim.y, i = row_base((r), j_) + k_)
+// (the walk of a range — row_base, row_thread, ARMON_FOR_RANGE — is range_walk.hpp)
 
 // ---- a1: perfect_gas_EOS! (ref src/kernels.jl:4-13) ------------------------------------------------
 template <typename T>

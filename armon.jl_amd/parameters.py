@@ -102,16 +102,20 @@ class ArmonParameters:
     # ref src/parameters.jl:632-670
     def _init_test(self, test="Sod", domain_size=None, origin=None, cfl=0., maxtime=0.,
                    maxcycle=500_000, **options):
+        """``test``: the name of a built-in case, or a ``problem.Problem`` — a user-defined initial state, gamma, EOS and
+        boundary types — which is bound here to the run's data type and cell size (``Problem.bind``)."""
+        from .problem import Problem
+        problem = test if isinstance(test, Problem) else None
         name = str(test)
         if domain_size is None:
-            domain_size = default_domain_size(name)
+            domain_size = problem.domain_size if problem is not None else default_domain_size(name)
         self.domain_size = tuple(float(d) for d in domain_size)
         if origin is None:
-            origin = default_domain_origin(name)
+            origin = problem.origin if problem is not None else default_domain_origin(name)
         self.origin = tuple(float(o) for o in origin)
         T = self.T
         dX = (T(self.domain_size[0]) / T(self.N[0]), T(self.domain_size[1]) / T(self.N[1]))
-        self.test = create_test(name, dX, T)
+        self.test = problem.bind(dX, T, self.N) if problem is not None else create_test(name, dX, T)
         self.maxcycle = int(maxcycle)
         self.cfl = float(cfl) if cfl != 0 else self.test.cfl
         self.maxtime = float(maxtime) if maxtime != 0 else self.test.maxtime
@@ -137,6 +141,9 @@ class ArmonParameters:
         self.reorder_grid = reorder_grid
         self.gpu_aware = gpu_aware
         self.global_comm = global_comm
+        if self.use_MPI and getattr(self.test, "arrays", None) is not None:
+            solver_error("config", "Problem.from_arrays is not supported for ranks of a process group (use_MPI=true): "
+                                   "one block or an in-process tile group only")
         if self.use_MPI:
             import torch.distributed as dist
             if not dist.is_initialized():
@@ -361,8 +368,8 @@ class ArmonParameters:
         if self.start_from_exact is not None and self.restart_from is not None:
             solver_error("config", "start_from_exact cannot be combined with restart_from: both set the initial state and the clock")
         if self.exact_solution:
-            from .analytic import NO_CLOSED_FORM
-            if self.test.name in NO_CLOSED_FORM:
+            from .analytic import has_closed_form
+            if not has_closed_form(self.test):
                 solver_error("config", f"error_norms_step / error_norms_at_end / start_from_exact need a test case with an exact "
                                        f"solution: {self.test.name} has no closed form")
         if isinstance(history_step, bool) or not isinstance(history_step, (numbers.Integral, np.integer)) or history_step < 0:

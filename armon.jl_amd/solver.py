@@ -570,6 +570,11 @@ def _init_test_kernel(params, grid):
     check(params.fn("init_test")(params.device.ctx, _range(params, full), params.test.tag,
                                    bs.size[0], bs.size[1], bs.ghosts, C.byref(gpos), C.byref(gN),
                                    C.byref(origin), C.byref(dX), params.test.r, C.byref(bd)))
+    if getattr(params.test, "is_problem", False):
+        # a user-defined problem (problem.py): init_test above wrote x, y, mask and the zeroed work vectors; rho, u, v, E are
+        # overwritten from the problem's regions (armon_hip_init_regions) or arrays
+        from .problem import init_state
+        init_state(params, grid)
 
 
 def update_EOS(params, grid, axis=Axis.X):

@@ -225,6 +225,40 @@ ARMON_API int armon_hip_init_test(armon_ctx*, armon_range, int test, int64_t row
         int nghost, const int64_t global_pos[2], const int64_t global_N[2],
         const double origin[2], const double dX[2], double sedov_r, const armon_block_data* data);
 
+/* User-defined initial states (csrc/init_regions.hip; no reference counterpart): a background state
+ * and a list of regions, each with a state of its own. OVERWRITES rho, u, v, E on `range` (ghost cells included when the
+ * range holds them, as init_test does over the full domain) and nothing else: a host first calls armon_hip_init_test with
+ * any two-state tag for x, y, mask and the zeroed work vectors, then this. row_length, nghost, global_pos, origin, dX as for
+ * armon_hip_init_test. A cell's state depends on its GLOBAL position only, so tiles and ghost widths change no bit.
+ * All arithmetic in the data type, one IEEE operation per operation written, comparisons inclusive:
+ *   corner   x = (T)gx dX[0] + origin[0],  y likewise (init_test's own formulas)
+ *   samples  xs_i = x + dX[0] T((2 i + 1) / (2 samples)), i = 0 .. samples - 1, the same along y: samples^2 points per cell
+ *            (samples = 1: init_test's x + dX/2, bit for bit)
+ *   HALF_PLANE  a0 xs + a1 ys <= a2
+ *   BOX         a0 <= xs && xs <= a1 && a2 <= ys && ys <= a3      (+-inf = an open side)
+ *   DISC        (xs - a0)(xs - a0) + (ys - a1)(ys - a1) <= a2      (a2 = r^2)
+ *   ELLIPSE     (xs - a0)(xs - a0) a2 + (ys - a1)(ys - a1) a3 <= 1 (a2, a3 = 1/rx^2, 1/ry^2, rounded by the caller)
+ * A point belongs to the LAST region of the list that holds it, to the background if none does. A cell whose samples all
+ * belong to the same region (or all to the background) stores that state verbatim. Any other cell accumulates, y sample
+ * outer, x sample inner, m += rho, mu += rho u, mv += rho v, mE += rho E and stores rho = m / T(samples^2), u = mu / m,
+ * v = mv / m, E = mE / m: the conservative mix of mass, momentum and total energy.
+ * Refused (ARMON_ERR_INVALID_ARG, before any launch, nothing written): a NULL pointer, nregions outside 0 .. 32, an unknown
+ * kind, samples not 1, 2, 4 or 8, a NaN anywhere, an infinity anywhere but in the bounds of a BOX, a rho <= 0, an origin or
+ * dX that is not finite, dX <= 0. `background` and `regions` are HOST memory, read before the call returns (the table is a
+ * kernel argument: no allocation, no copy, no synchronisation). Async on the context's stream. */
+enum { ARMON_REGION_HALF_PLANE = 0, ARMON_REGION_BOX = 1, ARMON_REGION_DISC = 2, ARMON_REGION_ELLIPSE = 3 };
+typedef struct { int32_t kind, reserved; double a[4]; double rho, u, v, E; } armon_region;
+typedef struct { int32_t kind, reserved; float a[4]; float rho, u, v, E; } armon_region_f32;
+
+ARMON_API int armon_hip_init_regions(armon_ctx*, armon_range, int64_t row_length, int nghost,
+        const int64_t global_pos[2], const double origin[2], const double dX[2], int samples,
+        const double background[4] /* rho, u, v, E */, int nregions, const armon_region* regions,
+        double* rho, double* u, double* v, double* E);
+ARMON_API int armon_hip_init_regions_f32(armon_ctx*, armon_range, int64_t row_length, int nghost,
+        const int64_t global_pos[2], const float origin[2], const float dX[2], int samples,
+        const float background[4], int nregions, const armon_region_f32* regions,
+        float* rho, float* u, float* v, float* E);
+
 /* ---- in-situ reduced output (no reference counterpart: the reference writes whole fields, ref src/io.jl:2-27) ---- */
 /* Conservative coarsening of one block by the integer factors (fx, fy) >= 1. The block has rows of `row_length` elements,
  * `nghost` ghost layers and nx x ny real cells (row_length >= nx + 2 nghost); only real cells are read. Coarse cell (I, J)
