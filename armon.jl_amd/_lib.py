@@ -238,6 +238,8 @@ SIGNATURES = {
     "armon_hip_tune_placement": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.POINTER(_vp), _ci,
                                        C.c_size_t, _ci, C.POINTER(_ci * 8), C.POINTER(_dbl)]),
     "armon_hip_cycle_xy": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc)]),
+    "armon_hip_sweep_pair_pitch": (C.c_int64, [C.c_int64, _ci]),
+    "armon_hip_sweep_pair": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.c_size_t]),
     "armon_hip_choose_placement": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.POINTER(_vp), _ci,
                                          C.c_size_t, _ci, _dbl, C.POINTER(_ci * 8), C.POINTER(_dbl), C.POINTER(_ci)]),
     "armon_hip_mgpu_init": (_ci, [_ci, _ci, C.POINTER(_ci), C.POINTER(_vp)]),
@@ -306,15 +308,18 @@ def _add_f32_signatures():
 _add_f32_signatures()
 
 
-def load_at(path):
+def load_at(path, missing_ok=()):
     """Load one build of the library and declare every entry point (used for the default build, and by
-    tools/ab_sweep.py to time several builds side by side)."""
+    tools/ab_sweep.py to time several builds side by side; ``missing_ok``: entry points an OLDER build it compares
+    against may lack)."""
     if not os.path.exists(path):
         raise RuntimeError(
             f"{path} is missing: build it with `python armon.jl_amd/build.py` "
             "(there is no CPU fallback for the device backend)")
     L = C.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in missing_ok and not hasattr(L, name):
+            continue
         fn = getattr(L, name)   # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

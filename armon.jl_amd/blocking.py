@@ -135,6 +135,16 @@ class DomainRange:
         return Range(self.col.first - 1, self.col.step, len(self.col), self.row.first - 1, len(self.row))
 
 
+LINE_BYTES = 128          # cache line of the part's L2 / MALL
+
+
+def line_pitch(nx, nghost, itemsize=8):
+    """``nx + 2·nghost`` elements rounded up to a whole number of 128-B lines: every row of such an array starts on a
+    line when the array does. The ghost offsets stay what they are — cell (x, y) at ``(y + g)·pitch + x + g``."""
+    per_line = LINE_BYTES // itemsize
+    return -(-(nx + 2 * nghost) // per_line) * per_line
+
+
 @dataclass(frozen=True)
 class BlockSize:
     """ref StaticBSize/DynamicBSize (src/blocking/blocking.jl:19-66): ``size`` includes the ghosts."""
@@ -148,6 +158,15 @@ class BlockSize:
     @property
     def n_cells(self):
         return self.size[0] * self.size[1]
+
+    def line_pitch(self, itemsize=8):
+        """Row pitch, in elements, of the state BETWEEN the X and the Y sweep of a Sequential cycle
+        (``armon_hip_sweep_pair_pitch``): the block's own pitch rounded up to a whole 128-B line."""
+        return line_pitch(self.real_size[0], self.ghosts, itemsize)
+
+    def line_cells(self, itemsize=8):
+        """Elements a vector needs to hold the block at that pitch (>= ``n_cells``)."""
+        return self.line_pitch(itemsize) * self.size[1]
 
     # ref src/blocking/blocking.jl:71-85
     def domain_range(self, bottom_left=(0, 0), top_right=(0, 0)):

@@ -34,7 +34,9 @@ struct armon_ctx {
     int tune_x_rows = 0;             // ARMON_X_ROWS: workgroup of the X sweep = 1: one strip of 4 rows, 2: 4 strips of one row, 0: by precision
     int tune_copy_nt = 0;            // ARMON_COPY_NT: the measurement aid armon_hip_stream_copy4 with nt loads (bit 0) / stores (bit 1)
     int tune_y_sx = 0;               // ARMON_Y_SX: store exchange of the Y march = 1: always, 2: never, 0: when the row pitch is not a multiple of a sector
-    int tune_profile_wgs = 0;        // PROFILE_WGS: cap on the workgroups of the profile kernels (0 = automatic); changes no result bit
+    int tune_y_nt = 0;               // ARMON_Y_NT: non-temporal row loads of the Y march = 2: never, 0: when its input rows are whole 128-B lines
+    int tune_pair_only = 0;          // ARMON_PAIR_ONLY: armon_hip_sweep_pair enqueues 1: its X sweep only, 2: its Y sweep only (A/B timing), 0: both
+    int tune_profile_wgs = 0;       // PROFILE_WGS: cap on the workgroups of the profile kernels (0 = automatic); changes no result bit
     // y_run_length's last answer (it depends on the shape only)
     int64_t seg_nx = -1, seg_ny = -1;
     int seg_lag = -1, seg_cols = -1, seg_value = 0;

@@ -102,7 +102,7 @@ int armon_hip_init(int device_id, void* stream, armon_ctx** out)
     }
     int rc = ensure_partials(ctx, 8192);
     if (rc != ARMON_OK) { armon_hip_destroy(ctx); return rc; }
-    for (const char* knob : {"ARMON_XS_NITER", "ARMON_Y_SEG", "ARMON_SWEEP_ALIGN", "ARMON_Y_COLS1", "ARMON_X_XCD", "ARMON_X_ROWS", "ARMON_Y_SX", "ARMON_COPY_NT"}) {
+    for (const char* knob : {"ARMON_XS_NITER", "ARMON_Y_SEG", "ARMON_SWEEP_ALIGN", "ARMON_Y_COLS1", "ARMON_X_XCD", "ARMON_X_ROWS", "ARMON_Y_SX", "ARMON_Y_NT", "ARMON_COPY_NT"}) {
         const char* v = getenv(knob);
         if (v && *v) (void)armon_hip_set_tuning(ctx, knob, atoi(v));
     }
@@ -120,6 +120,8 @@ int armon_hip_set_tuning(armon_ctx* ctx, const char* knob, int value)
     else if (!strcmp(knob, "ARMON_X_XCD")) ctx->tune_x_xcd = value < 0 ? -1 : (value > 0);
     else if (!strcmp(knob, "ARMON_X_ROWS")) ctx->tune_x_rows = (value == 1 || value == 2) ? value : 0;
     else if (!strcmp(knob, "ARMON_Y_SX")) ctx->tune_y_sx = (value == 1 || value == 2) ? value : 0;
+    else if (!strcmp(knob, "ARMON_Y_NT")) ctx->tune_y_nt = value == 2 ? 2 : 0;
+    else if (!strcmp(knob, "ARMON_PAIR_ONLY")) ctx->tune_pair_only = (value == 1 || value == 2) ? value : 0;
     else if (!strcmp(knob, "ARMON_COPY_NT")) ctx->tune_copy_nt = value & 3;
     else if (!strcmp(knob, "PROFILE_WGS")) ctx->tune_profile_wgs = value > 0 ? value : 0;
     else ARMON_REQUIRE(false, "unknown tuning knob '%s'", knob);
@@ -136,6 +138,8 @@ int armon_hip_get_tuning(armon_ctx* ctx, const char* knob, int* value)
     else if (!strcmp(knob, "ARMON_X_XCD")) *value = ctx->tune_x_xcd;
     else if (!strcmp(knob, "ARMON_X_ROWS")) *value = ctx->tune_x_rows;
     else if (!strcmp(knob, "ARMON_Y_SX")) *value = ctx->tune_y_sx;
+    else if (!strcmp(knob, "ARMON_Y_NT")) *value = ctx->tune_y_nt;
+    else if (!strcmp(knob, "ARMON_PAIR_ONLY")) *value = ctx->tune_pair_only;
     else if (!strcmp(knob, "ARMON_COPY_NT")) *value = ctx->tune_copy_nt;
     else if (!strcmp(knob, "PROFILE_WGS")) *value = ctx->tune_profile_wgs;
     else if (!strcmp(knob, "Y_RUN_ROWS")) *value = ctx->tune_y_seg > 0 ? ctx->tune_y_seg : ctx->seg_value;

@@ -11,13 +11,13 @@
 //  * sweep_x_kernel.hpp: X sweep, spatial form (k_sweep_x_dpp): lane ↔ cell(s) of a row, neighbours fetched with
 //    DPP wavefront shifts (sweep_spatial.hpp); no LDS, no barrier, coalesced 16-B accesses.
 //  * fused_sweep_alt_kernels.hpp / fused_sweep_alt_cycle.hpp (-DARMON_ALT_KERNELS): k_sweep_x_lds, k_cycle_xy / k_cycle_pc.
-//  * placement.hip: armon_hip_tune_placement / armon_hip_choose_placement (they call armon_hip_sweep).
+//  * placement.hip: armon_hip_tune_placement / armon_hip_choose_placement (they call armon_hip_sweep / armon_hip_sweep_pair).
 // Redundant work is confined to the LAG (≤4) cells at both ends of a run / strip. Block and strip origins are
 // aligned to the 64-B sectors of the ghosted rows, stores are non-temporal (profiles/NOTES.md has the A/B numbers).
 // Tuning knobs (tools/ab_sweep.py, parity tests), read from the environment once per context or set with
-// armon_hip_set_tuning: ARMON_SWEEP_ALIGN, ARMON_XS_NITER, ARMON_Y_SEG, ARMON_Y_COLS1, ARMON_Y_SX, ARMON_X_XCD, ARMON_X_ROWS;
+// armon_hip_set_tuning: ARMON_SWEEP_ALIGN, ARMON_XS_NITER, ARMON_Y_SEG, ARMON_Y_COLS1, ARMON_Y_SX, ARMON_Y_NT, ARMON_X_XCD, ARMON_X_ROWS, ARMON_PAIR_ONLY;
 // compile-time: ARMON_NT_X, ARMON_NT_Y, ARMON_Y_PF, ARMON_Y_PRIO, ARMON_Y_WAVES, ARMON_Y_BLOCK, ARMON_XS_ROWS, ARMON_XS_WAVES,
-// ARMON_X_PRIO, ARMON_X_PRELOAD, ARMON_PROBE_NOCOMPUTE, ARMON_ONLY_HEADLINE.
+// ARMON_X_PRIO, ARMON_X_PRELOAD, ARMON_PROBE_NOCOMPUTE, ARMON_ONLY_HEADLINE, ARMON_Y_NT_ALL.
 #pragma once
 #include "sweep_device.hpp"
 #include "sweep_y_kernel.hpp"
@@ -40,8 +40,10 @@ struct y_shape {
     int cols = 1;                    // columns per lane
     int block = kYBlock;             // lanes per workgroup
     bool sx = false;                 // rows stored through LDS (sweep_args::y_sx)
+    bool nt = false;                 // rows loaded non-temporally (y_nt_loads; the flavours without that form ignore it)
 };
-y_shape y_launch_shape(const armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
+// `in_len`, `out_len`: pitch of the rows the march reads / writes
+y_shape y_launch_shape(const armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int64_t in_len, int64_t out_len)
 {
     y_shape s;
     // fp32, tuned arithmetic: two columns per lane when every row is 8-B aligned (even pitch and ghost width): half the
@@ -52,10 +54,17 @@ y_shape y_launch_shape(const armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
     // arithmetic only: the exact flavour is bound by its arithmetic (§4.2) and is not instantiated with the exchange.
     if (ctx->tune_align != 0 && ctx->tune_y_sx != 2 && !d->exact) {
         const uintptr_t outs = (uintptr_t)d->rho_out | (uintptr_t)d->u_out | (uintptr_t)d->v_out | (uintptr_t)d->E_out;
-        const int64_t row_len = d->nx + 2 * (int64_t)d->nghost;
-        s.sx = outs % 64 == 0 && ((row_len * (int64_t)sizeof(real)) % 64 != 0 || ctx->tune_y_sx == 1);
+        s.sx = outs % 64 == 0 && ((out_len * (int64_t)sizeof(real)) % 64 != 0 || ctx->tune_y_sx == 1);
     }
     s.block = s.sx ? kYSxBlock : kYBlock;
+    // Non-temporal row loads when every row the march reads starts on a 128-B line: a wave's 512-B segment (the block origin
+    // is shifted onto a line, a.xshift) then shares no line with its neighbours. The intermediate of armon_hip_sweep_pair
+    // is laid out for it; a block whose own pitch is whole lines qualifies as it stands. ARMON_Y_NT = 2: never (A/B).
+    {
+        const uintptr_t ins = (uintptr_t)d->rho_in | (uintptr_t)d->u_in | (uintptr_t)d->v_in | (uintptr_t)d->E_in;
+        s.nt = ctx->tune_align != 0 && ctx->tune_y_nt != 2 && s.cols == 1 && !s.sx && ins % 128 == 0 &&
+               (in_len * (int64_t)sizeof(real)) % 128 == 0;
+    }
     return s;
 }
 
@@ -80,6 +89,12 @@ int launch(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape& ys, int
             if (ys.sx) {
                 hipLaunchKernelGGL((k_sweep_y<PIPE, TRACK, kYSxBlock, true>), grid, dim3(ys.block), 0, ctx->stream, a);
                 return check_launch("sweep_y (store exchange)");
+            }
+        }
+        if constexpr (y_nt_loads(PIPE::EOS, PIPE::kExact)) {
+            if (ys.nt) {
+                hipLaunchKernelGGL((k_sweep_y<PIPE, TRACK, kYBlock, false, 1, true>), grid, dim3(ys.block), 0, ctx->stream, a);
+                return check_launch("sweep_y (nt loads)");
             }
         }
         hipLaunchKernelGGL((k_sweep_y<PIPE, TRACK>), grid, dim3(ys.block), 0, ctx->stream, a);
@@ -226,7 +241,9 @@ int dispatch_proj(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape& 
 
 }  // namespace
 
-extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
+// One sweep of the block `d` describes, reading arrays of pitch `in_len` and writing arrays of pitch `out_len` (cell (x, y) at
+// (y + g)·pitch + x + g in both). armon_hip_sweep: both are the block's own nx + 2g.
+static int sweep_pitched(armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int64_t in_len, int64_t out_len)
 {
     ARMON_REQUIRE(ctx && d, "NULL argument");
     ARMON_REQUIRE(d->axis == ARMON_AXIS_X || d->axis == ARMON_AXIS_Y, "invalid axis %d", d->axis);
@@ -271,7 +288,8 @@ extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
     sweep_args a;
     a.nx = d->nx;
     a.ny = d->ny;
-    a.row_len = d->nx + 2 * (int64_t)d->nghost;
+    a.row_len = in_len;
+    a.out_len = out_len;
     a.g = d->nghost;
     a.bc_low = d->bc_low;
     a.bc_high = d->bc_high;
@@ -298,7 +316,7 @@ extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
     a.c_out = d->c_out;
     a.st = d->dt_state;
     const bool align = ctx->tune_align != 0;
-    const y_shape ys = X ? y_shape{} : y_launch_shape(ctx, d);
+    const y_shape ys = X ? y_shape{} : y_launch_shape(ctx, d, in_len, out_len);
     a.y_sx = ys.sx;
     if (X) {
         a.seg = 512;
@@ -315,7 +333,7 @@ extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
         a.seg = ctx->seg_value;
     }
     // the Y march addresses a run of rows with 32-bit byte offsets from the run's first row
-    ARMON_REQUIRE(X || a.row_len * (int64_t)sizeof(real) * (a.seg + 2 * lag + 16) < (1ll << 32),
+    ARMON_REQUIRE(X || (in_len > out_len ? in_len : out_len) * (int64_t)sizeof(real) * (a.seg + 2 * lag + 16) < (1ll << 32),
                   "block too wide for 32-bit row offsets (%lld cells per row, runs of %d rows)", (long long)d->nx, a.seg);
     a.x_kernel = d->x_kernel;
     a.o_lo = 0;
@@ -348,7 +366,7 @@ extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
         const uintptr_t bases = (uintptr_t)d->rho_in | (uintptr_t)d->u_in | (uintptr_t)d->v_in | (uintptr_t)d->E_in |
                                 (uintptr_t)d->rho_out | (uintptr_t)d->u_out | (uintptr_t)d->v_out | (uintptr_t)d->E_out |
                                 (uintptr_t)d->p_out | (uintptr_t)d->c_out;
-        a.x_row_align = X && align && d->x_kernel == 0 && ctx->tune_xs_niter <= 1 && a.row_len % (64 / (int64_t)sizeof(real)) != 0 &&
+        a.x_row_align = X && align && d->x_kernel == 0 && ctx->tune_xs_niter <= 1 && a.out_len % (64 / (int64_t)sizeof(real)) != 0 &&
                         bases % 64 == 0;
     }
 #endif
@@ -393,6 +411,52 @@ extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
     return fold_dt_launch(ctx, a.partials, n_blocks, (real)d->cfl_dx, (real)d->cfl_dy, d->dt_cfl_out, d->dt_accumulate, d->dt_state);
 #endif
 }
+
+extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)
+{
+    ARMON_REQUIRE(ctx && d, "NULL argument");
+    const int64_t pitch = d->nx + 2 * (int64_t)d->nghost;
+    return sweep_pitched(ctx, d, pitch, pitch);
+}
+
+// ---- the X and the Y sweep of one Sequential cycle, the state between them in rows of whole 128-B lines ----------------
+// Nobody outside looks at the X sweep's output before the Y sweep has consumed it, so its layout is the library's: the
+// ghost offsets are kept — cell (x, y) at (y + g)·P + x + g — and the pitch P is nx + 2g rounded up to a whole line. Every
+// row the Y march reads then starts on a line, which is what its non-temporal loads need (y_launch_shape); the 32-B phase
+// between the X sweep's loads and its sector-aligned stores, and the strip origins, are what they are with one pitch.
+#ifdef ARMON_PAIR_FN
+extern "C" int64_t ARMON_PAIR_PITCH_FN(int64_t nx, int nghost)
+{
+    const int64_t line = 128 / (int64_t)sizeof(real);
+    return (nx + 2 * (int64_t)nghost + line - 1) / line * line;
+}
+
+extern "C" int ARMON_PAIR_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* x, const ARMON_SWEEP_DESC* y, size_t mid_bytes)
+{
+    ARMON_REQUIRE(ctx && x && y, "NULL argument");
+    ARMON_REQUIRE(x->axis == ARMON_AXIS_X && y->axis == ARMON_AXIS_Y, "the pair is an X sweep followed by a Y sweep");
+    ARMON_REQUIRE(x->nx == y->nx && x->ny == y->ny && x->nghost == y->nghost && x->nx > 0 && x->ny > 0 && x->nghost >= 0,
+                  "the two descriptors describe different blocks");
+    ARMON_REQUIRE(x->rho_out == y->rho_in && x->u_out == y->u_in && x->v_out == y->v_in && x->E_out == y->E_in && x->rho_out,
+                  "the Y sweep must read the arrays the X sweep writes");
+    // the Y march then reads real cells only (mirror rows come from inside the block): no ghost of the intermediate is ever read
+    ARMON_REQUIRE(y->bc_low && y->bc_high, "a block with a remote Y side cannot use the pair (its ghost rows come from a neighbour)");
+    ARMON_REQUIRE(x->out_hi == 0 && y->out_hi == 0, "the pair runs whole sweeps");
+    ARMON_REQUIRE(!x->p_out && !x->c_out && !x->dt_cfl_out, "the X sweep of the pair has no output of its own");
+    ARMON_REQUIRE(x->x_kernel == 0, "x_kernel form %d cannot write the intermediate layout", x->x_kernel);
+    const int64_t pitch = x->nx + 2 * (int64_t)x->nghost, mid = ARMON_PAIR_PITCH_FN(x->nx, x->nghost);
+    ARMON_REQUIRE((uint64_t)mid_bytes >= (uint64_t)(mid * (x->ny + 2 * (int64_t)x->nghost)) * sizeof(real),
+                  "the intermediate arrays hold %zu bytes, rows of %lld cells need %lld", mid_bytes, (long long)mid,
+                  (long long)(mid * (x->ny + 2 * (int64_t)x->nghost) * (int64_t)sizeof(real)));
+    // ARMON_PAIR_ONLY (A/B tools): 1 = the X sweep alone, 2 = the Y sweep alone (on the intermediate an earlier call left)
+    if (ctx->tune_pair_only != 2) {
+        const int rc = sweep_pitched(ctx, x, pitch, mid);
+        if (rc != ARMON_OK) return rc;
+    }
+    if (ctx->tune_pair_only != 1) return sweep_pitched(ctx, y, mid, pitch);
+    return ARMON_OK;
+}
+#endif
 
 // ---- whole cycle (X sweep then Y sweep, Sequential splitting) in one launch: k_cycle_xy --------------------------------
 #if defined(ARMON_CYCLE_FN) && !defined(ARMON_ALT_KERNELS)

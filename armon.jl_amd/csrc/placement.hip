@@ -2,7 +2,7 @@
 // ---- placement of the 8 streamed vectors -------------------------------------------------------
 // The same sweeps run 10-20 % apart depending on where the 4 read and 4 written vectors sit in HBM relative to each
 // other, and nothing visible from user space predicts it: time `tries` assignments of the 8 roles to the vectors of
-// `pool` (the first one = pool[0..7] as given) with the caller's own X and Y sweeps, as in a cycle — X reads
+// `pool` (the first one = pool[0..7] as given) with the caller's own X and Y sweeps, as in a cycle (cycle_f64 / cycle_f32 below) — X reads
 // roles 0..3 and writes roles 4..7, Y reads 4..7 and writes 0..3 — and report the fastest.
 #include "common.hpp"
 
@@ -20,6 +20,31 @@ __global__ void __launch_bounds__(256) k_fill_uniform(real* __restrict__ p, size
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) p[i] = value;
 }
+
+// What a draw is timed with: the X and the Y sweep of a cycle as the host will run them. fp64: a cycle that satisfies
+// armon_hip_sweep_pair's preconditions on vectors that hold its intermediate runs through that call — other pitch of the
+// rows between the sweeps, other load policy in the Y march, hence another access pattern to choose a placement for.
+struct cycle_f64 {
+    size_t bytes;
+    int operator()(armon_ctx* ctx, const armon_sweep_desc* x, const armon_sweep_desc* y) const
+    {
+        const int64_t rows = x->ny + 2 * (int64_t)x->nghost;
+        const bool pair = x->axis == ARMON_AXIS_X && y->axis == ARMON_AXIS_Y && x->nx == y->nx && x->ny == y->ny &&
+                          x->nghost == y->nghost && x->nx > 0 && x->ny > 0 && x->nghost >= 0 && y->bc_low && y->bc_high &&
+                          x->out_hi == 0 && y->out_hi == 0 && !x->p_out && !x->c_out && !x->dt_cfl_out && x->x_kernel == 0 &&
+                          (uint64_t)bytes >= (uint64_t)(armon_hip_sweep_pair_pitch(x->nx, x->nghost) * rows) * sizeof(double);
+        if (pair) return armon_hip_sweep_pair(ctx, x, y, bytes);
+        const int rc = armon_hip_sweep(ctx, x);
+        return rc == ARMON_OK ? armon_hip_sweep(ctx, y) : rc;
+    }
+};
+struct cycle_f32 {
+    int operator()(armon_ctx* ctx, const armon_sweep_desc_f32* x, const armon_sweep_desc_f32* y) const
+    {
+        const int rc = armon_hip_sweep_f32(ctx, x);
+        return rc == ARMON_OK ? armon_hip_sweep_f32(ctx, y) : rc;
+    }
+};
 
 // The search both entry points share. `prepare(idx)` readies the pool for the assignment idx[0..7] before it is timed,
 // `stop(seen, best_ms)` ends the search early; both return ARMON_OK / false to go on. *tries_done = draws timed.
@@ -59,8 +84,7 @@ int placement_search(armon_ctx* ctx, SWEEP sweep, const DESC* x_desc, const DESC
         double ms_min = 1e300;
         for (int rep = 0; rep < 3; rep++) {
             PLACEMENT_TRY(hipEventRecord(e0, ctx->stream));
-            rc = sweep(ctx, &dx);
-            if (rc == ARMON_OK) rc = sweep(ctx, &dy);
+            rc = sweep(ctx, &dx, &dy);
             if (rc != ARMON_OK) { cleanup(); return rc; }
             PLACEMENT_TRY(hipEventRecord(e1, ctx->stream));
             PLACEMENT_TRY(hipEventSynchronize(e1));
@@ -175,20 +199,20 @@ int choose_placement(armon_ctx* ctx, SWEEP sweep, const DESC* x_desc, const DESC
 extern "C" int armon_hip_tune_placement(armon_ctx* ctx, const armon_sweep_desc* x_desc, const armon_sweep_desc* y_desc,
                                         void* const* pool, int n_pool, size_t bytes, int tries, int* picks, double* times_ms)
 {
-    return tune_placement(ctx, armon_hip_sweep, x_desc, y_desc, pool, n_pool, bytes, tries, picks, times_ms);
+    return tune_placement(ctx, cycle_f64{bytes}, x_desc, y_desc, pool, n_pool, bytes, tries, picks, times_ms);
 }
 
 extern "C" int armon_hip_tune_placement_f32(armon_ctx* ctx, const armon_sweep_desc_f32* x_desc, const armon_sweep_desc_f32* y_desc,
                                             void* const* pool, int n_pool, size_t bytes, int tries, int* picks, double* times_ms)
 {
-    return tune_placement(ctx, armon_hip_sweep_f32, x_desc, y_desc, pool, n_pool, bytes, tries, picks, times_ms);
+    return tune_placement(ctx, cycle_f32{}, x_desc, y_desc, pool, n_pool, bytes, tries, picks, times_ms);
 }
 
 extern "C" int armon_hip_choose_placement(armon_ctx* ctx, const armon_sweep_desc* x_desc, const armon_sweep_desc* y_desc,
                                           void* const* pool, int n_pool, size_t bytes, int tries, double tolerance, int* picks,
                                           double* times_ms, int* tries_done)
 {
-    return choose_placement<double>(ctx, armon_hip_sweep, x_desc, y_desc, pool, n_pool, bytes, tries, tolerance, picks, times_ms,
+    return choose_placement<double>(ctx, cycle_f64{bytes}, x_desc, y_desc, pool, n_pool, bytes, tries, tolerance, picks, times_ms,
                                     tries_done);
 }
 
@@ -196,6 +220,6 @@ extern "C" int armon_hip_choose_placement_f32(armon_ctx* ctx, const armon_sweep_
                                               void* const* pool, int n_pool, size_t bytes, int tries, double tolerance, int* picks,
                                               double* times_ms, int* tries_done)
 {
-    return choose_placement<float>(ctx, armon_hip_sweep_f32, x_desc, y_desc, pool, n_pool, bytes, tries, tolerance, picks,
+    return choose_placement<float>(ctx, cycle_f32{}, x_desc, y_desc, pool, n_pool, bytes, tries, tolerance, picks,
                                    times_ms, tries_done);
 }

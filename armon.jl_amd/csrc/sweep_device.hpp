@@ -68,7 +68,8 @@ __device__ __forceinline__ void st2(real* p, real x, real y)
 }
 
 struct sweep_args {
-    int64_t nx, ny, row_len;       // real cells and array pitch (nx + 2g)
+    int64_t nx, ny, row_len;       // real cells and pitch of the arrays the sweep READS (nx + 2g; the pair's intermediate: line_pitch())
+    int64_t out_len;               // pitch of the arrays it WRITES (p_out / c_out included); cell (x, y) sits at (y + g)·pitch + x + g in both
     int32_t g;                     // ghost layers
     int32_t bc_low, bc_high;       // mirror BC applied in-kernel on that side of the sweep axis
     int32_t emit;                  // bit 0: write p_out, bit 1: write c_out
@@ -160,6 +161,12 @@ template <>
 __device__ __forceinline__ double buf_load<double>(rsrc_t r, unsigned voff, unsigned soff)
 {
     const v2u v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, kAuxLoad);
+    return __builtin_bit_cast(double, v);
+}
+// the Y march's non-temporal row loads (y_nt_loads in sweep_y_kernel.hpp): the ordinary policy + nt
+__device__ __forceinline__ double buf_load_nt(rsrc_t r, unsigned voff, unsigned soff)
+{
+    const v2u v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, kAuxLoad | 2);
     return __builtin_bit_cast(double, v);
 }
 template <>

@@ -69,12 +69,16 @@ __device__ __forceinline__ void sweep_x_dpp_body(const sweep_args& a, int niter)
                                   : ((int64_t)vby * kXSRows + threadIdx.y) * RW + (ROW ? (threadIdx.x >> 4) : 0);
     const bool row_ok = row_r < a.ny;                         // whole wave (ROW: a row of 16 lanes)
     const int64_t row = row_ok ? row_r : a.ny - 1;
-    const int64_t row_off = (row + a.g) * a.row_len + a.g;
-    const real* in[4] = {a.rho_in + row_off, a.ua_in + row_off, a.ut_in + row_off, a.E_in + row_off};
+    // the row in the arrays the sweep reads and in those it writes: one pitch for a plain sweep, two for the pair's X sweep,
+    // whose output is the intermediate of whole lines per row (armon_hip_sweep_pair)
+    const int64_t row_in = (row + a.g) * a.row_len + a.g;
+    const int64_t row_off = (row + a.g) * a.out_len + a.g;
+    const real* in[4] = {a.rho_in + row_in, a.ua_in + row_in, a.ut_in + row_in, a.E_in + row_in};
     real* out[4] = {a.rho_out + row_off, a.ua_out + row_off, a.ut_out + row_off, a.E_out + row_off};
     // 16-B accesses need every lane pair on an even cell of an even-pitched row; strip origins are multiples of 8 cells
     // from the row start (x_first), so an odd o_lo (partial sweeps with LAG = 3) only masks half of one pair
-    bool vec_ok = (K == 2) && (a.row_len % 2 == 0) && ((a.x_first + a.g) % 2 == 0);         // uniform
+    bool vec_ok = (K == 2) && (a.out_len % 2 == 0) && ((a.x_first + a.g) % 2 == 0);         // uniform: the stores
+    bool vec_in = (K == 2) && (a.row_len % 2 == 0) && ((a.x_first + a.g) % 2 == 0);         // uniform: the loads
     // When the row pitch is not a multiple of a sector (8 doubles, 16 floats) the rows start at different places of their 64-B sectors and no single
     // origin aligns them all (fp64 at 16388 cells per row: X 1.05x the copy, profiles/r03_row_pitch.txt): the origin is then
     // taken row by row, less than a sector below o_lo, where that row's stores start on a sector (arrays start on one). Every
@@ -85,6 +89,8 @@ __device__ __forceinline__ void sweep_x_dpp_body(const sweep_args& a, int niter)
         // 64-bit vector arithmetic — +3 % on the VALU-bound exact flavour)
         x_first = a.o_lo - __builtin_amdgcn_readfirstlane((int)(row_off + a.o_lo) & (64 / (int)sizeof(real) - 1));
         vec_ok = (K == 2);
+        // (the stores decide the origin; with one pitch the loads sit on the same 16 B)
+        vec_in = (K == 2) && __builtin_amdgcn_readfirstlane((int)(row_in + x_first) & 1) == 0;
     }
 
     SW sw{a.dt, a.dx, a.gamma, a.inv_dx, a.dt_dx};
@@ -104,7 +110,7 @@ __device__ __forceinline__ void sweep_x_dpp_body(const sweep_args& a, int niter)
         const int64_t cb = w_first + (int64_t)it * STRIDE - HALO;     // first cell of the strip
         const int64_t j0 = cb + (int64_t)lane * K;                    // this lane's first cell
         const bool interior = cb >= 0 && cb + WIDTH <= a.nx;          // uniform: no ghost, no clamping
-        if (interior && (K == 1 || vec_ok)) {
+        if (interior && (K == 1 || vec_in)) {
             if (K == 2) {
                 constexpr bool NT = x_nt_loads(EOS, EXACT);
                 const vec2 r = ld2<NT>(in[0] + j0);
@@ -225,7 +231,7 @@ __device__ __forceinline__ void sweep_x_dpp_body(const sweep_args& a, int niter)
 __device__ __forceinline__ void preload_x_args(const sweep_args& a, int niter)
 {
 #if ARMON_X_PRELOAD
-    asm volatile("" ::"s"(a.nx), "s"(a.ny), "s"(a.row_len), "s"(a.g), "s"(a.bc_low), "s"(a.bc_high), "s"(a.emit), "s"(a.o_lo),
+    asm volatile("" ::"s"(a.nx), "s"(a.ny), "s"(a.row_len), "s"(a.out_len), "s"(a.g), "s"(a.bc_low), "s"(a.bc_high), "s"(a.emit), "s"(a.o_lo),
                  "s"(a.o_hi), "s"(a.x_first), "s"(a.xcd_remap), "s"(a.x_wg_along_x), "s"(a.x_row_align), "s"(niter), "s"(a.gx), "s"(a.gy));
     asm volatile("" ::"s"(a.dt), "s"(a.dx), "s"(a.gamma), "s"(a.inv_dx), "s"(a.dt_dx), "s"(a.rho_in), "s"(a.ua_in), "s"(a.ut_in),
                  "s"(a.E_in), "s"(a.rho_out), "s"(a.ua_out), "s"(a.ut_out), "s"(a.E_out));

@@ -29,7 +29,12 @@ template <class PIPE> struct y_lane<1, PIPE> {
     using V = real;
     using pipe_t = PIPE;
     using lds_t = real;              // element of the store exchange
-    static __device__ __forceinline__ V load(rsrc_t r, unsigned voff, unsigned soff) { return buf_load<real>(r, voff, soff); }
+    template <bool NT = false>
+    static __device__ __forceinline__ V load(rsrc_t r, unsigned voff, unsigned soff)
+    {
+        if constexpr (NT && std::is_same<real, double>::value) return buf_load_nt(r, voff, soff);
+        else return buf_load<real>(r, voff, soff);
+    }
     static __device__ __forceinline__ void store(rsrc_t r, unsigned voff, unsigned soff, V v) { buf_store(r, voff, soff, v); }
     static __device__ __forceinline__ void track(cfl_track& t, const V& u, const V& v, const V& c) { t.add(u, v, c); }
 };
@@ -48,7 +53,20 @@ template <class PIPE> struct y_lane<2, PIPE> {
     }
 };
 
-template <class PIPE, bool TRACK, int BLOCK = kYBlock, bool SX = false, int COLS = 1>
+// Which instantiations of the march exist with non-temporal row loads (NTL; ARMON_NT_Y above is the policy of all the
+// others). The host chooses the form per launch, when every row the march READS is a whole number of 128-B lines from the
+// next (launch() in fused_sweep.hpp): a wave's 512-B segment then shares no line with its neighbours, and a line that is
+// not kept is not fetched twice (profiles/r05_ab_nt.txt §5, profiles/y_line_pitch_ab.txt). The tuned fp64 perfect-gas
+// march only: the flavour it was measured to pay for, as for the X sweep (x_nt_loads).
+constexpr bool y_nt_loads(int eos, bool exact)
+{
+#ifdef ARMON_Y_NT_ALL            // A/B builds (tools/build_variant.sh): every fp64 flavour
+    return sizeof(real) == 8;
+#endif
+    return sizeof(real) == 8 && eos == ARMON_EOS_PERFECT_GAS && !exact;
+}
+
+template <class PIPE, bool TRACK, int BLOCK = kYBlock, bool SX = false, int COLS = 1, bool NTL = false>
 __global__ void __launch_bounds__(BLOCK, ARMON_Y_WAVES)
 k_sweep_y(sweep_args a)
 {
@@ -72,8 +90,10 @@ k_sweep_y(sweep_args a)
     // Descriptors are based at the first row this run touches, so every scalar row offset is a small
     // non-negative 32-bit number whatever the size of the arrays (mirrored rows lie inside the run).
     const unsigned colb = (unsigned)(x + g) * (unsigned)sizeof(real);
-    const unsigned pitchb = (unsigned)a.row_len * (unsigned)sizeof(real);
-    const int64_t in_base = (int64_t)(jb + g) * a.row_len, out_base = (int64_t)(o0 + g) * a.row_len;
+    // pitch of the rows it reads and of the rows it writes: the same number for a plain sweep; the pair's Y march reads an
+    // intermediate of whole lines per row (armon_hip_sweep_pair)
+    const unsigned pitchb = (unsigned)a.row_len * (unsigned)sizeof(real), opitchb = (unsigned)a.out_len * (unsigned)sizeof(real);
+    const int64_t in_base = (int64_t)(jb + g) * a.row_len, out_base = (int64_t)(o0 + g) * a.out_len;
     const rsrc_t r_rho = make_rsrc(a.rho_in + in_base), r_ua = make_rsrc(a.ua_in + in_base);
     const rsrc_t r_ut = make_rsrc(a.ut_in + in_base), r_E = make_rsrc(a.E_in + in_base);
     const rsrc_t w_rho = make_rsrc(a.rho_out + out_base), w_ua = make_rsrc(a.ua_out + out_base);
@@ -84,7 +104,7 @@ k_sweep_y(sweep_args a)
 
     int lj = jb;                     // next row to load and its offset from the run's first row
     unsigned lo_off = 0;
-    unsigned so_off = (unsigned)(jb - LAG - o0) * pitchb;     // row j - LAG relative to row o0 (wraps until valid)
+    unsigned so_off = (unsigned)(jb - LAG - o0) * opitchb;    // row j - LAG relative to row o0 (wraps until valid)
 
     // Store exchange (SX, chosen by sweep_args::y_sx; rows that do not all start on 64-B sectors, i.e. a pitch that is not a multiple of a sector).
     // A lane's column is fixed for the whole march, so on such rows every wave's 512-B store would begin and end inside a
@@ -97,10 +117,11 @@ k_sweep_y(sweep_args a)
     // COLS = 2: in units of a lane's column PAIR (8 B; eight pairs per sector).
     __shared__ typename lane_t::lds_t sx_lds[SX ? 2 : 1][SX ? 4 : 1][SX ? BLOCK : 1];
     static_assert((BLOCK & (BLOCK - 1)) == 0, "the store exchange wraps columns with a mask");
+    static_assert(!NTL || (COLS == 1 && !SX), "non-temporal row loads: the one-column march without the store exchange");
     constexpr int kSec = 64 / (COLS * (int)sizeof(real));    // lane units (cells, pairs) per sector
     const int c0 = (int)(blockIdx.x * BLOCK) * COLS - a.xshift;   // first column of the workgroup (COLS = 2: even)
-    int sx_r = (int)((((int64_t)(jb - LAG + g) * a.row_len + g + c0) >> (COLS - 1)) & (kSec - 1));    // phase of row j - LAG, j = jb
-    const int sx_dr = (int)((a.row_len >> (COLS - 1)) & (kSec - 1));
+    int sx_r = (int)((((int64_t)(jb - LAG + g) * a.out_len + g + c0) >> (COLS - 1)) & (kSec - 1));    // phase of row j - LAG, j = jb
+    const int sx_dr = (int)((a.out_len >> (COLS - 1)) & (kSec - 1));
     int sx_buf = 0;
 
     // The state of row lj is loaded straight into the pipeline's cell ring, slot lj mod 8, PF steps before
@@ -147,19 +168,19 @@ k_sweep_y(sweep_args a)
                 const unsigned off = (unsigned)(src - jb) * pitchb;
                 const real fa = m_lo ? a.fa_low : (m_hi ? a.fa_high : real(1));
                 const real ft = m_lo ? a.ft_low : (m_hi ? a.ft_high : real(1));
-                dst.rho = lane_t::load(r_rho, colb, off);
-                dst.ua = lane_t::load(r_ua, colb, off) * fa;
-                dst.ut = lane_t::load(r_ut, colb, off) * ft;
-                dst.E = lane_t::load(r_E, colb, off);
+                dst.rho = lane_t::template load<NTL>(r_rho, colb, off);
+                dst.ua = lane_t::template load<NTL>(r_ua, colb, off) * fa;
+                dst.ut = lane_t::template load<NTL>(r_ut, colb, off) * ft;
+                dst.E = lane_t::template load<NTL>(r_E, colb, off);
                 if (lj + 1 < je) {       // stay on the last row once the run is exhausted (padding steps)
                     lj++;
                     lo_off += pitchb;
                 }
             } else {
-                dst.rho = lane_t::load(r_rho, colb, lo_off);
-                dst.ua = lane_t::load(r_ua, colb, lo_off);
-                dst.ut = lane_t::load(r_ut, colb, lo_off);
-                dst.E = lane_t::load(r_E, colb, lo_off);
+                dst.rho = lane_t::template load<NTL>(r_rho, colb, lo_off);
+                dst.ua = lane_t::template load<NTL>(r_ua, colb, lo_off);
+                dst.ut = lane_t::template load<NTL>(r_ut, colb, lo_off);
+                dst.E = lane_t::template load<NTL>(r_E, colb, lo_off);
                 lj++;
                 lo_off += pitchb;
             }
@@ -187,7 +208,7 @@ k_sweep_y(sweep_args a)
         const int o = j - LAG;
         if (CHECKED) {
             if (a.emit && j >= o0 && j < o1 && active) {
-                const unsigned off = so_off + LAG * pitchb;
+                const unsigned off = so_off + LAG * opitchb;
                 if (a.emit & 1) lane_t::store(make_rsrc(a.p_out + out_base), colb, off, p);
                 if (a.emit & 2) lane_t::store(make_rsrc(a.c_out + out_base), colb, off, c);
             }
@@ -233,7 +254,7 @@ k_sweep_y(sweep_args a)
             }
             if (TRACK) lane_t::track(cfl, out.ut, out.ua, c_lag);      // Y sweep: ut = u, ua = v
         }
-        so_off += pitchb;
+        so_off += opitchb;
         sx_r = (sx_r + sx_dr) & (kSec - 1);
     };
     auto run = [&](auto checked, int t0, int t1) {           // steps [t0, t1), both multiples of 8

@@ -104,8 +104,8 @@ class HIPDevice:
         return ms.value
 
     # array constructors ------------------------------------------------------------------------
-    def empty(self, n, dtype=np.float64):
-        return DeviceArray(self, n, dtype)
+    def empty(self, n, dtype=np.float64, capacity=None):
+        return DeviceArray(self, n, dtype, capacity)
 
     def zeros(self, n, dtype=np.float64):
         a = DeviceArray(self, n, dtype)
@@ -122,13 +122,16 @@ class HIPDevice:
 class DeviceArray:
     """Flat 1-D device vector: the ``V{T,1}(undef, n)`` of ref src/blocking/blocks.jl:36-44."""
 
-    def __init__(self, device, n, dtype=np.float64):
+    def __init__(self, device, n, dtype=np.float64, capacity=None):
+        """``capacity`` (elements, >= n): allocate that many while the vector stays one of ``n`` elements for every copy and
+        view — room behind it that only the library uses (the line-pitched intermediate of ``armon_hip_sweep_pair``)."""
         self.device = device
         self.n = int(n)
         self.dtype = np.dtype(dtype)
         self.nbytes = self.n * self.dtype.itemsize
+        self._capacity_bytes = max(self.n, int(capacity or 0)) * self.dtype.itemsize
         p = C.c_void_p()
-        check(device._L.armon_hip_malloc(device.ctx, self.nbytes, C.byref(p)))
+        check(device._L.armon_hip_malloc(device.ctx, self.capacity_bytes, C.byref(p)))
         self.ptr = p.value or 0
 
     @classmethod
@@ -144,6 +147,11 @@ class DeviceArray:
 
     def __len__(self):
         return self.n
+
+    @property
+    def capacity_bytes(self):
+        """Bytes behind ``ptr`` that belong to this vector (``nbytes`` unless it was created with a ``capacity``)."""
+        return getattr(self, "_capacity_bytes", self.nbytes)
 
     @property
     def __cuda_array_interface__(self):

@@ -127,7 +127,10 @@ class _Fields(dict):
         import weakref
         self._grid_ref = weakref.ref(grid)     # no reference cycle: a dropped grid must release its vectors at once (86 GB blocks follow each other in the tests)
         for f in names:
-            self[f] = grid.params.device.empty(grid.size.n_cells, grid.params.data_type)
+            # the state vectors are interchangeable with their ping-pong partners (placement): all of them hold the pair's
+            # line-pitched intermediate when the block's cycles run through it
+            self[f] = grid.params.device.empty(grid.size.n_cells, grid.params.data_type,
+                                               capacity=grid.pair_cells if f in STATE_VARS else None)
 
     def __missing__(self, key):
         if key not in FIELDS:
@@ -145,6 +148,19 @@ class _Fields(dict):
         return a
 
 
+def pair_usable(params):
+    """The X and the Y sweep of a cycle can go through ``armon_hip_sweep_pair`` — the state between them in rows of whole
+    128-B lines, which the Y march loads non-temporally — when the cycle is the library's from end to end: fused fp64
+    sweeps, Sequential splitting (X then Y, every cycle), no remote side (a neighbour's ghost rows would have to arrive in
+    the intermediate layout), and a block large enough for the placement of its vectors to be measured
+    (``placement_min_bytes`` per vector: smaller ones gain nothing from either and keep the plain layout). Decided once per block (its vectors are allocated with room for that layout); ``pair_cycle``
+    decides cycle by cycle."""
+    return bool(params.use_fused_sweep and np.dtype(params.data_type).itemsize == 8 and params.axis_splitting == "Sequential"
+                and not params.use_MPI and all(n == PROC_NULL for n in params.neighbours.values())
+                and int(getattr(params, "x_kernel", 0)) == 0
+                and params.block_size.n_cells * np.dtype(params.data_type).itemsize >= params.placement_min_bytes)
+
+
 class BlockGrid:
     """One block per GPU (ref BlockGrid with use_cache_blocking=false, src/blocking/block_grid.jl:352-355):
     the 16 ``BlockData`` vectors (ref src/blocking/blocks.jl:18-44) in HBM, plus the 4 ping-pong state
@@ -158,8 +174,10 @@ class BlockGrid:
         dt_ = params.data_type
         self.initialised = False               # init_test has run (a vector created later is given its initial content)
         self.lazy = set()                      # fused path: the vectors created on first access
+        # elements per state vector when the cycles run through armon_hip_sweep_pair (about 1 MB more per vector at 16384²)
+        self.pair_cells = self.size.line_cells(np.dtype(dt_).itemsize) if pair_usable(params) else None
         self.data = _Fields(self, FUSED_FIELDS if params.use_fused_sweep else FIELDS)
-        self.alt = {f: dev.empty(n, dt_) for f in STATE_VARS} if params.use_fused_sweep else None
+        self.alt = {f: dev.empty(n, dt_, capacity=self.pair_cells) for f in STATE_VARS} if params.use_fused_sweep else None
         self.placement = None                  # report of tune_placement (bench / tests)
         self.global_dt = GlobalTimeStep(params)
         self.dt_scalar = dev.zeros(2, dt_)     # device scalar written by the fused dt reduction
@@ -238,9 +256,13 @@ class BlockGrid:
         dt = 1e-3 * dx                    # any small step: the arithmetic does not depend on the data
         n, dt_ = self.data["rho"].n, self.data["rho"].dtype
         pool = [self.data[f] for f in STATE_VARS] + [self.alt[f] for f in STATE_VARS]
+        # every vector of the pool can end up in any role: the spares are as large as the grid's own, and the library sees
+        # the whole allocation — it times the draws with armon_hip_sweep_pair when they hold its intermediate
+        cap = min(v.capacity_bytes for v in pool) // dt_.itemsize
+        cap_bytes = cap * dt_.itemsize
         try:
             for _ in range(spare):
-                pool.append(dev.empty(n, dt_))
+                pool.append(dev.empty(n, dt_, capacity=cap))
         except _lib.SolverException:          # not enough memory after all: keep the placement we have
             for v in pool[8:]:
                 v.free()
@@ -266,10 +288,10 @@ class BlockGrid:
             picks, times, done = (C.c_int * 8)(), (C.c_double * tries)(), C.c_int(tries)
             try:
                 if keep_state:
-                    check(params.fn("tune_placement")(dev.ctx, C.byref(d_x), C.byref(d_y), ptrs, len(pool), nbytes, tries,
+                    check(params.fn("tune_placement")(dev.ctx, C.byref(d_x), C.byref(d_y), ptrs, len(pool), cap_bytes, tries,
                                                       C.byref(picks), times))
                 else:
-                    check(params.fn("choose_placement")(dev.ctx, C.byref(d_x), C.byref(d_y), ptrs, len(pool), nbytes,
+                    check(params.fn("choose_placement")(dev.ctx, C.byref(d_x), C.byref(d_y), ptrs, len(pool), cap_bytes,
                                                         tries, 0.004, C.byref(picks), times, C.byref(done)))
             except _lib.SolverException:          # e.g. no room for the 4 transient vectors: nothing was moved in THIS round
                 # pool[:8] is the assignment this round started from — the grid's own vectors in round 1, the best of the
@@ -290,7 +312,7 @@ class BlockGrid:
             if free < (spare + 2) * nbytes:
                 break
             try:
-                pool = best + [dev.empty(n, dt_) for _ in range(spare)]
+                pool = best + [dev.empty(n, dt_, capacity=cap) for _ in range(spare)]
             except _lib.SolverException:
                 break
         for k, f in enumerate(STATE_VARS):
@@ -456,7 +478,9 @@ class BlockGrid:
         """Bytes of device memory the block's vectors take (ref memory_required, src/blocking/block_grid.jl): the 16 of
         ``BlockData`` on the staged path; 7 + 4 ping-pong partners on the fused one (+ any created on first access)."""
         n = self.size.n_cells * np.dtype(self.params.data_type).itemsize
-        return n * (len(self.data) + (4 if self.alt else 0))
+        # (+ the padding of the 8 state vectors that hold the line-pitched intermediate of armon_hip_sweep_pair)
+        pad = sum(v.capacity_bytes - v.nbytes for v in list(self.data.values()) + (list(self.alt.values()) if self.alt else []))
+        return n * (len(self.data) + (4 if self.alt else 0)) + pad
 
 
 # ---- per-block kernel wrappers -----------------------------------------------------------------
@@ -718,6 +742,20 @@ def fused_sweep(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=
         grid.swap_state()
 
 
+def pair_cycle(params, grid):
+    """This cycle's X and Y sweeps go through ``armon_hip_sweep_pair``: ``pair_usable``, no kernel callbacks to wrap around
+    the single sweeps, and vectors that hold its intermediate (a grid whose vectors were replaced by smaller ones falls back
+    to the two plain sweeps)."""
+    return (grid.pair_cells is not None and not params.kernel_callbacks and pair_usable(params)
+            and min(grid.alt[f].capacity_bytes for f in STATE_VARS) >= grid.pair_cells * np.dtype(params.data_type).itemsize)
+
+
+def fused_pair(params, grid, d_x, d_y):
+    """``armon_hip_sweep_pair``: ``d_x`` sweeps the current state into the alternate vectors, ``d_y`` sweeps it back."""
+    mid = min(v.capacity_bytes for v in list(grid.alt.values()) + [grid.data[f] for f in STATE_VARS])
+    check(params.fn("sweep_pair")(params.device.ctx, C.byref(d_x), C.byref(d_y), mid))
+
+
 def sweep_desc(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=False, out_range=None,
                dt_accumulate=False):
     """The ``armon_sweep_desc`` of one sweep of ``grid``'s current state into its alternate arrays."""
@@ -949,6 +987,21 @@ def solver_cycle(params, grid, last_cycle=True):
         grid.comm.native_cycle(gdt, last_cycle)
         return False
     sweeps = split_axes(params.axis_splitting, gdt.cycle)
+    if params.use_fused_sweep and pair_cycle(params, grid):
+        # the cycle is the library's from end to end: X then Y through armon_hip_sweep_pair, the state between them in rows of
+        # whole lines; the Y sweep emits what a cycle's last sweep emits below
+        dt = gdt.current_dt
+        d_x = sweep_desc(params, grid, Axis.X, dt * params.T(sweeps[0][1]), params.cell_size(0))
+        grid.swap_state()
+        d_y = sweep_desc(params, grid, Axis.Y, dt * params.T(sweeps[1][1]), params.cell_size(1), emit_p=last_cycle,
+                         emit_dt=not params.cst_dt)
+        grid.swap_state()
+        fused_pair(params, grid, d_x, d_y)
+        if not params.cst_dt:
+            post_dt_readback(params, grid)
+            if deferred:
+                gdt.update_dt(take_dt_readback(params, grid, gdt.cycle - 1))
+        return False
     for k, (axis, dt_factor) in enumerate(sweeps):
         # update_solver_state!: ref src/solver_state.jl:339-345
         i_ax = int(axis) - 1
@@ -1075,8 +1128,12 @@ def time_loop_graph(params, grid, _after_handover=None):
         dummy.free()
 
         def enqueue_cycle(parity):
-            for d in _graph_sweep_descs(params, grid, parity, state.ptr):
-                check(params.fn("sweep")(dev.ctx, C.byref(d)))
+            descs = _graph_sweep_descs(params, grid, parity, state.ptr)
+            if pair_cycle(params, grid):          # the same two kernels and the fold, the intermediate in rows of whole lines
+                fused_pair(params, grid, *descs)
+            else:
+                for d in descs:
+                    check(params.fn("sweep")(dev.ctx, C.byref(d)))
             if not auto:
                 check(step(dev.ctx, C.c_void_p(state.ptr), L_new, float(params.cfl), float(params.maxtime), params.maxcycle,
                            int(params.cst_dt), float(params.Dt)))

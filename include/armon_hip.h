@@ -99,7 +99,9 @@ ARMON_API void* armon_hip_stream(armon_ctx* ctx);                              /
  * workgroups share their lines themselves), "ARMON_X_ROWS" workgroup shape of the X sweep: 1 = one strip of
  * 4 rows, 2 = 4 consecutive strips of one row, 0 = automatic (the former for fp64, the latter for fp32),
  * "ARMON_Y_SX" store exchange of the Y march (rows stored in sector-aligned windows handed over through LDS): 1 = always,
- * 2 = never, 0 = automatic (when the row pitch is not a multiple of a 64-B sector), "ARMON_COPY_NT" the measurement aid
+ * 2 = never, 0 = automatic (when the row pitch is not a multiple of a 64-B sector), "ARMON_Y_NT" non-temporal row loads of the
+ * Y march: 2 = never, 0 = automatic (when the rows it reads are whole 128-B lines apart), "ARMON_PAIR_ONLY" armon_hip_sweep_pair
+ * enqueues 1 = its X sweep only, 2 = its Y sweep only, 0 = both (not read from the environment), "ARMON_COPY_NT" the measurement aid
  * armon_hip_stream_copy4 with non-temporal loads (bit 0) / stores (bit 1), "PROFILE_WGS" cap on the workgroups of
  * armon_hip_profile / armon_hip_profile_bounds, 0 = automatic (not read from the environment).
  * None of them changes a result bit. */
@@ -820,6 +822,20 @@ ARMON_API int armon_hip_graph_destroy(armon_graph* graph);
  * ARMON_ERR_INVALID_ARG. No reference counterpart. */
 ARMON_API int armon_hip_cycle_xy(armon_ctx*, const armon_sweep_desc* x_desc, const armon_sweep_desc* y_desc);
 
+/* The X sweep and the Y sweep of one Sequential cycle of a block, with the state BETWEEN them in a layout of the library's
+ * own: rows of armon_hip_sweep_pair_pitch(nx, nghost) elements — nx + 2·nghost rounded up to a whole 128-B line — with the
+ * ghost offsets kept, cell (x, y) at (y + nghost)·pitch + x + nghost. Every row the Y march reads then starts on a line and
+ * it loads them non-temporally (tuned fp64 perfect gas; the other flavours run their ordinary kernels on the same layout).
+ * Precondition: x_desc->*_out == y_desc->*_in — those four arrays, of `mid_bytes` bytes each, must hold
+ * pitch·(ny + 2·nghost) elements; nothing but the two sweeps may rely on their content (the padding is never written). The
+ * caller's own arrays, x_desc->*_in and y_desc->*_out, keep the pitch nx + 2·nghost. Both sweeps are whole (out_lo = out_hi
+ * = 0), the Y sides are physical boundaries (bc_low, bc_high: a remote side's ghost rows would have to arrive in the
+ * intermediate layout), the X sweep emits nothing of its own (p_out, c_out, dt_cfl_out NULL). Enqueues exactly what
+ * armon_hip_sweep(x_desc) followed by armon_hip_sweep(y_desc) would — graph capture and dt_state included — and leaves the
+ * same bits in y_desc->*_out, p_out, c_out and dt_cfl_out. fp64 only. No reference counterpart. */
+ARMON_API int64_t armon_hip_sweep_pair_pitch(int64_t nx, int nghost);
+ARMON_API int armon_hip_sweep_pair(armon_ctx*, const armon_sweep_desc* x_desc, const armon_sweep_desc* y_desc, size_t mid_bytes);
+
 /* Placement of the 8 vectors a fused sweep streams (4 read + 4 written). On MI355X the same sweeps run 10-20 %
  * apart depending on where these vectors sit in HBM relative to each other (back-to-back allocations end up at a
  * regular physical spacing that makes the 8 streams collide on channels/banks), so a host
@@ -830,7 +846,10 @@ ARMON_API int armon_hip_cycle_xy(armon_ctx*, const armon_sweep_desc* x_desc, con
  * other fields of x_desc / y_desc are used as they are (dt_cfl_out included), their 8 state pointers are ignored.
  * On return picks[role] = index in `pool` of the vector to use for that role, the state lives in pool[picks[0..3]],
  * every other vector of the pool is free for the caller to release; times_ms (nullable, [tries]) = the best
- * X+Y time of each assignment. Synchronous; needs 4 more vectors of `bytes` transiently. No reference counterpart. */
+ * X+Y time of each assignment. Synchronous; needs 4 more vectors of `bytes` transiently. No reference counterpart.
+ * fp64: when the descriptors satisfy armon_hip_sweep_pair's preconditions and `bytes` holds its intermediate, the draws are
+ * timed with that call — the pitch and load policy such a host's cycles run — instead of two armon_hip_sweep calls (the
+ * same holds for armon_hip_choose_placement). */
 ARMON_API int armon_hip_tune_placement(armon_ctx*, const armon_sweep_desc* x_desc, const armon_sweep_desc* y_desc,
         void* const* pool, int n_pool, size_t bytes, int tries, int picks[8], double* times_ms);
 

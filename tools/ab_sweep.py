@@ -30,6 +30,10 @@ ap.add_argument("--track-x", action="store_true", help="fused dt/CFL reduction o
 ap.add_argument("--no-track-y", action="store_true", help="Y sweep without the fused dt/CFL reduction (a cycle's first sweep in Y-first splittings)")
 ap.add_argument("--env", default="", help="per-build tuning knobs: name:KEY=VAL,KEY=VAL;name2:... (armon_hip_set_tuning on that build's context)")
 ap.add_argument("--gap-ms", type=float, default=0., help="idle time before every launch (clock/power recovery experiments)")
+ap.add_argument("--pair", action="store_true",
+                help="a cycle's roles, X: data -> alt, Y: alt -> a third set, for every build; the builds that export "
+                     "armon_hip_sweep_pair run both through it (ARMON_PAIR_ONLY = 1 / 2: the intermediate at the line pitch, "
+                     "the Y march's load policy that follows from it), the others through armon_hip_sweep on the standard layout")
 ap.add_argument("--copy", action="store_true", help="also time armon_hip_stream_copy4 on the same arrays (same bytes, no arithmetic)")
 ap.add_argument("libs", nargs="+", help="name=path")
 args = ap.parse_args()
@@ -49,7 +53,7 @@ for part in filter(None, args.env.split(";")):
 builds = []
 for spec in args.libs:
     name, path = spec.split("=", 1)
-    L = _lib.load_at(os.path.abspath(path))
+    L = _lib.load_at(os.path.abspath(path), missing_ok=("armon_hip_sweep_pair", "armon_hip_sweep_pair_pitch"))
     ctx = C.c_void_p()
     _lib.check(L.armon_hip_init(0, None, C.byref(ctx)))
     builds.append((name, L, ctx))
@@ -58,18 +62,39 @@ from armon_amd.solver import STATE_VARS
 src = (C.c_void_p * 4)(*[grid.data[f].ptr for f in STATE_VARS])
 dst = (C.c_void_p * 4)(*[grid.alt[f].ptr for f in STATE_VARS])
 nbytes = grid.data["rho"].nbytes & ~15
+third = None
+if args.pair:
+    # the Y sweep of a cycle reads what the X sweep wrote: a third set of vectors takes its output, so that no launch changes
+    # what another one reads (whichever layout the last X sweep left in `alt`: the kernels' work does not depend on the values)
+    cap = grid.alt["rho"].capacity_bytes // grid.alt["rho"].dtype.itemsize
+    third = {f: params.device.empty(grid.alt[f].n, grid.alt[f].dtype, capacity=cap) for f in STATE_VARS}
+    for f in STATE_VARS:
+        _lib.check(builds[0][1].armon_hip_memcpy(builds[0][2], C.c_void_p(grid.alt[f].ptr), C.c_void_p(grid.data[f].ptr),
+                                                 grid.data[f].nbytes, 3))
 res = {}
 knobs = sorted({k for e in envs.values() for k in e})
 for r in range(args.rounds + 2):
     for axis in (Axis.X, Axis.Y):
         d = sweep_desc(params, grid, axis, dt, dx, emit_dt=(axis == Axis.Y and not args.no_track_y) or (axis == Axis.X and args.track_x))
+        if args.pair:
+            d_x = sweep_desc(params, grid, Axis.X, dt, dx)
+            d_y = sweep_desc(params, grid, Axis.Y, dt, dx, emit_dt=not args.no_track_y)
+            d_y.rho_in, d_y.u_in, d_y.v_in, d_y.E_in = d_x.rho_out, d_x.u_out, d_x.v_out, d_x.E_out
+            d_y.rho_out, d_y.u_out, d_y.v_out, d_y.E_out = (third[f].ptr for f in STATE_VARS)
+            d = d_x if axis == Axis.X else d_y
         for name, L, ctx in builds:
             for k in knobs:                       # knobs live in the context: reset, then apply this build's values
                 _lib.check(L.armon_hip_set_tuning(ctx, k.encode(), int(envs.get(name, {}).get(k, -1 if k == "ARMON_SWEEP_ALIGN" else 0))))
             if args.gap_ms:
                 time.sleep(args.gap_ms * 1e-3)
+            paired = args.pair and hasattr(L, "armon_hip_sweep_pair")
+            if paired:
+                _lib.check(L.armon_hip_set_tuning(ctx, b"ARMON_PAIR_ONLY", 1 if axis == Axis.X else 2))
             _lib.check(L.armon_hip_event_record(ctx, 0))
-            _lib.check(getattr(L, "armon_hip_sweep" + params.suffix)(ctx, C.byref(d)))
+            if paired:
+                _lib.check(L.armon_hip_sweep_pair(ctx, C.byref(d_x), C.byref(d_y), grid.alt["rho"].capacity_bytes))
+            else:
+                _lib.check(getattr(L, "armon_hip_sweep" + params.suffix)(ctx, C.byref(d)))
             _lib.check(L.armon_hip_event_record(ctx, 1))
             ms = C.c_double()
             _lib.check(L.armon_hip_event_elapsed_ms(ctx, 0, 1, C.byref(ms)))
