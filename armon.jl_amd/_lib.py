@@ -207,6 +207,7 @@ SIGNATURES = {
     "armon_hip_init_regions_f32": (_ci, [_vp, Range, _i64, _ci, C.POINTER(_i64 * 2), C.POINTER(C.c_float * 2),
                                          C.POINTER(C.c_float * 2), _ci, C.POINTER(C.c_float * 4), _ci, C.POINTER(RegionF32)]
                                    + [_dp] * 4),
+    "armon_hip_body_force": (_ci, [_vp, Range, _dbl, _dbl, _dbl] + [_dp] * 3),
     "armon_hip_coarsen": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 6),
     "armon_hip_derive": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 4 + [C.POINTER(DeriveSpec), _dp]),
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),
@@ -266,6 +267,7 @@ SIGNATURES = {
     "armon_hip_mgpu_cycle": (_ci, [_vp, C.POINTER(CyclePlan), C.POINTER(TileCycle)]),
     "armon_hip_mgpu_drain": (_ci, [_vp, C.POINTER(TileCycle)]),
     "armon_hip_mgpu_set_threads": (_ci, [_vp, _ci]),
+    "armon_hip_mgpu_set_body_force": (_ci, [_vp, _dbl, _dbl]),
     "armon_hip_mgpu_sync": (_ci, [_vp]),
     "armon_hip_halo_ranges": (_ci, [_i64, _i64, _ci, _ci, C.POINTER(Range), C.POINTER(Range), C.POINTER(_i64)]),
 }
@@ -277,7 +279,7 @@ def _add_f32_signatures():
     for name in ("perfect_gas_EOS", "bizarrium_EOS", "acoustic", "acoustic_GAD", "cell_update",
                  "advection_first_order", "advection_second_order", "euler_projection", "boundary_conditions",
                  "pack_to_array", "unpack_from_array", "dtCFL_async", "dtCFL", "conservation_vars", "init_test",
-                 "coarsen", "gather_strided", "state_pack", "state_unpack", "plane_encode", "plane_decode"):
+                 "coarsen", "gather_strided", "state_pack", "state_unpack", "plane_encode", "plane_decode", "body_force"):
         res, args = SIGNATURES["armon_hip_" + name]
         conv = []
         for a in args:

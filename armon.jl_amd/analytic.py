@@ -33,7 +33,10 @@ NO_CLOSED_FORM = ("Sod_circ", "Bizarrium", "DebugIndexes")
 
 def has_closed_form(test):
     """Whether ``reference_for`` knows the exact solution of ``test``: a built-in case by its name; a user-defined problem
-    (problem.py) when it is a one-dimensional perfect-gas Riemann problem at gamma = 7/5 (``BoundProblem.riemann_setup``)."""
+    (problem.py) when it is a one-dimensional perfect-gas Riemann problem at gamma = 7/5 (``BoundProblem.riemann_setup``).
+    Never under a body force: the solutions known here are those of the unforced equations."""
+    if tuple(getattr(test, "gravity", (0., 0.))) != (0., 0.):
+        return False
     if getattr(test, "is_problem", False):
         return test.riemann_setup() is not None
     return test.name not in NO_CLOSED_FORM

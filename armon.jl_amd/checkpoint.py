@@ -55,6 +55,9 @@ BIT_FIELDS = ("data_type", "N", "test", "domain_size", "origin", "periodic", "sc
 # only in the header of a user-defined problem (problem.py; "test" is then "Problem:<name>"): gamma as a hexfloat and the
 # sha256 of the problem's canonical description
 PROBLEM_FIELDS = ("gamma", "problem_digest")
+# only in the header of a run under a body force: two hexfloats, the (gx, gy) the device receives. A header
+# without the key is that of a run without a force — every header written before the option existed, byte for byte
+NO_GRAVITY = [float(0.).hex(), float(0.).hex()]
 
 
 # ---- digest (host restatement: tests, and files checked without a device) ------------------------------------------------
@@ -175,6 +178,9 @@ def _check_header(header, path):
             bad(f"{k} = {header.get(k)!r}")
     if "pending_dt" not in header or not (header["pending_dt"] is None or _is_hexfloat(header["pending_dt"])):
         bad(f"pending_dt = {header.get('pending_dt')!r}")
+    if "gravity" in header and not (isinstance(header["gravity"], list) and len(header["gravity"]) == 2
+                                    and all(_is_hexfloat(v) for v in header["gravity"])):
+        bad(f"gravity = {header['gravity']!r}")
     if ("initial_mass" in header or "initial_energy" in header) and not (
             _is_hexfloat(header.get("initial_mass")) and _is_hexfloat(header.get("initial_energy"))):
         bad("initial_mass / initial_energy")
@@ -192,13 +198,24 @@ def bit_options(params):
                "use_fused_sweep": fused, "exact_arithmetic": bool(params.exact_arithmetic) if fused else None}
     if getattr(test, "is_problem", False):      # a user-defined problem (problem.py): the headers of the built-in cases are untouched
         options.update(gamma=hexfloat(test.gamma), problem_digest=test.digest)
+    gravity = tuple(getattr(test, "gravity", (0., 0.)))
+    if gravity != (0., 0.):                     # a run under a body force: the headers of every other run are untouched
+        options.update(gravity=[hexfloat(g) for g in gravity])
     return options
+
+
+def check_same_gravity(params, header, what):
+    """A configuration error when ``header`` (a missing key = no force) and the run disagree on the body force."""
+    theirs, mine = header.get("gravity", NO_GRAVITY), bit_options(params).get("gravity", NO_GRAVITY)
+    if theirs != mine:
+        solver_error("config", f"{what} was written with gravity = {theirs!r}, this run has gravity = {mine!r}")
 
 
 def check_compatible(params, header, path):
     """A configuration error that names the first bit-deciding field on which the file and the run disagree, or a file that
     leaves nothing to run. ``nghost``, the decomposition, ``maxcycle``, ``maxtime`` and the output options are free."""
     mine = bit_options(params)
+    check_same_gravity(params, header, f"the checkpoint {path}")      # (first: a problem's digest holds its force too)
     for k in BIT_FIELDS + PROBLEM_FIELDS:
         if header.get(k) != mine.get(k):
             solver_error("config", f"the checkpoint {path} was written with {k} = {header.get(k)!r}, this run has "

@@ -23,6 +23,7 @@
 // Buffer layout on the wire = pack_to_array!'s (ref src/halo_exchange.jl:187-216), produced by the same kernels as
 // armon_hip_pack_to_array / armon_hip_unpack_from_array.
 #include "common.hpp"
+#include "cycle_kick.hpp"
 #include "tile_pool.hpp"
 
 #include <cmath>
@@ -163,6 +164,7 @@ struct armon_mgpu {
     int use_threads = -1;                        // -1: by the environment (ARMON_MGPU_THREADS, default on), 0 / 1
     // ARMON_MGPU_TIMING=1: host time of tile 0's part of the cycle steps, printed when the group is destroyed
     bool pack_on_compute = false;
+    double force[2] = {0., 0.};                  // armon_hip_mgpu_set_body_force: the kick that ends every cycle (0, 0 = none)
     int timing = -1;
     double t_host[8] = {};
     long n_cycles = 0;
@@ -721,11 +723,19 @@ template <> struct cycle_traits<double> {
     using desc = armon_sweep_desc;
     using tile = armon_tile_cycle;
     static int sweep(armon_ctx* c, const desc* d) { return armon_hip_sweep(c, d); }
+    static int kick(armon_ctx* c, armon_range r, double dt, double gx, double gy, double* u, double* v, double* E)
+    {
+        return armon_hip_body_force(c, r, dt, gx, gy, u, v, E);
+    }
 };
 template <> struct cycle_traits<float> {
     using desc = armon_sweep_desc_f32;
     using tile = armon_tile_cycle_f32;
     static int sweep(armon_ctx* c, const desc* d) { return armon_hip_sweep_f32(c, d); }
+    static int kick(armon_ctx* c, armon_range r, float dt, float gx, float gy, float* u, float* v, float* E)
+    {
+        return armon_hip_body_force_f32(c, r, dt, gx, gy, u, v, E);
+    }
 };
 
 struct host_timer {
@@ -984,6 +994,27 @@ int mgpu_cycle(armon_mgpu* g, const armon_cycle_plan* plan_, const typename cycl
             ARMON_HIP_TRY(hipEventRecord(t.e_dtdone, t.xfer));
             t.rec_dtdone = true;
             return ARMON_OK;
+        });
+    }
+    if (g->force[0] != 0. || g->force[1] != 0.) {
+        // The body-force kick (armon_hip_body_force) that ends the cycle: ONE launch per tile over all its real cells, on the
+        // COMPUTE stream. Ordering, without a new event: the last sweep's step above left on that stream either the whole
+        // sweep, or the interior followed by the wait for e_edge (edge_join_one), behind which the strips of the transfer
+        // stream are complete — so the kick finds every real cell swept, and only once. (Kicking the interior on the compute
+        // stream and each strip on the transfer stream would overlap them, but costs three small launches instead of one on
+        // the chain that bounds a small tile's cycle, and the strips are a few rows.) Behind the kick in stream order come
+        // the e_state record that the packs of the exchange posted ahead wait for (start_pack, below) — the neighbour
+        // receives kicked cells, bit for bit what its own kick produces, the force being uniform — and the next cycle's
+        // sweeps. The unpack of that exchange (transfer stream) writes ghost cells, the kick real cells: disjoint. The CFL
+        // scalars were written by the sweeps themselves: the next step is that of the velocities before the kick, and its
+        // reduction (e_intdt, recorded above) does not wait for the kick.
+        const double dt_cycle = cycle_step(plan);     // current_dt: the plan holds the steps of its sweeps only (cycle_kick.hpp)
+        const double gx = g->force[0], gy = g->force[1];      // (a step that is not finite is refused by the kick itself)
+        steps.push_back([=, &sw](size_t k) -> int {
+            tile_t& t = g->tiles[k];
+            const D& d = sw[(plan.n_sweeps - 1) * nt + k];
+            ARMON_HIP_TRY(hipSetDevice(t.device));
+            return cycle_traits<T>::kick(t.ctx, real_range(d.nx, d.ny, d.nghost), (T)dt_cycle, (T)gx, (T)gy, d.u_out, d.v_out, d.E_out);
         });
     }
     if (prefetch) {
@@ -1349,6 +1380,16 @@ int armon_hip_mgpu_set_threads(armon_mgpu* g, int on)
 {
     ARMON_REQUIRE(g, "NULL argument");
     g->use_threads = on < 0 ? -1 : (on != 0);
+    return ARMON_OK;
+}
+
+int armon_hip_mgpu_set_body_force(armon_mgpu* g, double gx, double gy)
+{
+    ARMON_REQUIRE(g, "NULL argument");
+    ARMON_REQUIRE(std::isfinite(gx), "gx is a NaN or an infinity");
+    ARMON_REQUIRE(std::isfinite(gy), "gy is a NaN or an infinity");
+    g->force[0] = gx;
+    g->force[1] = gy;
     return ARMON_OK;
 }
 

@@ -89,6 +89,8 @@ class NativeGroup:
             assert rank.value == p.rank and tuple(coords) == p.cart_coords
             assert [p.neighbours[s] for s in (Side.Left, Side.Right, Side.Bottom, Side.Top)] == list(nb)
             self.edges.append((C.c_void_p(L.armon_hip_mgpu_edge_ctx(self.handle, k)), int(L.armon_hip_mgpu_edge_dt(self.handle, k))))
+        if self.root.forced:        # the body force of the run: the library's own cycle ends with its kick
+            check(L.armon_hip_mgpu_set_body_force(self.handle, *self.root.gravity))
         self.dt = grids[0].dt       # tile 0 lands the global CFL step (solver.DtReadback)
         self._tcs = {}              # tile-cycle descriptors per ping-pong parity (key: where each tile's rho lives)
 
@@ -290,11 +292,17 @@ class TileGroup(NativeGroup):
                 continue
             last = k == len(sweeps) - 1
             S.overlapped_sweep(tiles, self, axis, dt, dx, emit_p=last and last_cycle, emit_dt=last and not p0.cst_dt)
+            if last:
+                for p, g in tiles:               # each tile kicks its own real cells, on its compute stream (strips joined)
+                    S.body_force(p, g, gdt.current_dt)
             if last and not p0.cst_dt:
                 self.dt_allreduce()
                 readback.post(gdt.cycle, scalar)
                 if deferred:
                     gdt.update_dt(readback.take(gdt.cycle - 1))
+        if not fused:
+            for p, g in tiles:
+                S.body_force(p, g, gdt.current_dt)
 
     def time_loop(self):
         """ref src/solver.jl:323-403"""

@@ -11,7 +11,7 @@ import numpy as np
 
 from ._lib import solver_error
 from .blocking import Axis, BlockSize, Side, compute_steps_ranges
-from .test_cases import create_test, default_domain_origin, default_domain_size
+from .test_cases import default_domain_origin, default_domain_size
 
 SCHEMES = {"Godunov": 0, "GAD": 1}                       # ref src/riemann_schemes.jl:5-6
 SCHEME_STENCIL = {"Godunov": 1, "GAD": 2}                # ref :17-18
@@ -101,10 +101,13 @@ class ArmonParameters:
 
     # ref src/parameters.jl:632-670
     def _init_test(self, test="Sod", domain_size=None, origin=None, cfl=0., maxtime=0.,
-                   maxcycle=500_000, **options):
+                   maxcycle=500_000, gravity=None, **options):
         """``test``: the name of a built-in case, or a ``problem.Problem`` — a user-defined initial state, gamma, EOS and
-        boundary types — which is bound here to the run's data type and cell size (``Problem.bind``)."""
-        from .problem import Problem
+        boundary types — which is bound here to the run's data type and cell size (``Problem.bind``).
+        ``gravity=(gx, gy)``: a uniform body force, applied on the device as a kick at the end of every cycle (DESIGN.md
+        §4.12); it overrides a problem's own, as ``domain_size`` and ``cfl`` do, and works with a built-in case too. The
+        values are rounded to the data type; ``params.test.gravity`` holds what the device receives."""
+        from .problem import Problem, bind_case
         problem = test if isinstance(test, Problem) else None
         name = str(test)
         if domain_size is None:
@@ -115,7 +118,12 @@ class ArmonParameters:
         self.origin = tuple(float(o) for o in origin)
         T = self.T
         dX = (T(self.domain_size[0]) / T(self.N[0]), T(self.domain_size[1]) / T(self.N[1]))
-        self.test = problem.bind(dX, T, self.N) if problem is not None else create_test(name, dX, T)
+        if problem is not None:
+            self.test = problem.bind(dX, T, self.N, gravity=gravity)
+        else:
+            self.test = bind_case(name, dX, T, gravity=(0., 0.) if gravity is None else gravity)
+        self.gravity = self.test.gravity
+        self.forced = self.gravity != (0., 0.)
         self.maxcycle = int(maxcycle)
         self.cfl = float(cfl) if cfl != 0 else self.test.cfl
         self.maxtime = float(maxtime) if maxtime != 0 else self.test.maxtime

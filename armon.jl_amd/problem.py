@@ -14,6 +14,7 @@ is when the values are rounded, a pressure becomes an energy, and the presets wh
 restarts keep their bit-for-bit guarantees.
 """
 import ctypes as C
+import dataclasses
 import hashlib
 import json
 import math
@@ -23,7 +24,7 @@ import numpy as np
 
 from ._lib import Region, RegionF32, check, solver_error
 from .blocking import Axis, Side
-from .test_cases import Dirichlet, FreeFlow, TestCase, _known
+from .test_cases import Dirichlet, FreeFlow, TestCase, _known, create_test
 
 HALF_PLANE, BOX, DISC, ELLIPSE = 0, 1, 2, 3        # ARMON_REGION_*
 MAX_REGIONS = 32
@@ -52,6 +53,42 @@ def _pair(v, what, finite=True):
         solver_error("config", f"{what} takes two numbers, got {v!r}")
     conv = _finite if finite else _number
     return conv(a, what), conv(b, what)
+
+
+def bind_gravity(gravity, T):
+    """The body force ``gravity = (gx, gy)`` as the device receives it: two finite numbers rounded to the data
+    type ``T`` (a zero of either sign becomes ``0.0``) → a pair of Python floats. Anything else is a configuration error."""
+    try:
+        gx, gy = gravity
+    except (TypeError, ValueError):
+        solver_error("config", f"gravity takes two finite numbers (gx, gy), got {gravity!r}")
+    out = []
+    for g in (gx, gy):
+        if isinstance(g, (bool, np.bool_)) or not isinstance(g, (numbers.Real, np.floating, np.integer)) or not math.isfinite(g):
+            solver_error("config", f"gravity takes two finite numbers (gx, gy), got {gravity!r}")
+        with np.errstate(over="ignore"):
+            r = float(T(g))
+        if not math.isfinite(r):
+            solver_error("config", f"gravity = {gravity!r} is not finite in {np.dtype(T).name}")
+        out.append(r if r != 0 else 0.)
+    return tuple(out)
+
+
+@dataclasses.dataclass(frozen=True)
+class BoundTestCase(TestCase):
+    """A built-in case bound to a run: the ``TestCase`` of ``create_test`` with the run's body force, rounded to its data type."""
+    gravity: tuple = (0., 0.)
+
+
+def bind_case(name, dX, T, gravity=(0., 0.)):
+    """``create_test(name, dX, T)`` with the body force ``gravity`` of the run (``bind_gravity``) → ``BoundTestCase``; a forced
+    case is not ``conservative``."""
+    case = create_test(name, dX, T)
+    gravity = bind_gravity(gravity, T)
+    kw = {f.name: getattr(case, f.name) for f in dataclasses.fields(case)}
+    if gravity != (0., 0.):
+        kw["conservative"] = False
+    return BoundTestCase(gravity=gravity, **kw)
 
 
 class State:
@@ -160,11 +197,15 @@ class Problem:
     ``(shape, State)`` of which the LAST one that holds a point gives its state. ``samples``: 1, 2, 4 or 8 points per cell
     and axis; a cell whose points do not all fall in the same region takes the conservative mix of their states.
     ``boundaries``: ``"Dirichlet"`` (a reflecting wall), ``"FreeFlow"``, or four of them (left, right, bottom, top).
-    ``domain_size``, ``origin``, ``cfl``, ``maxtime`` are defaults the options of ``ArmonParameters`` override."""
+    ``gravity = (gx, gy)``: a uniform body force, applied as a kick at the end of every cycle; a forced
+    problem is not held to energy conservation. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
+    the options of ``ArmonParameters`` override."""
 
     def __init__(self, name, background, regions=(), gamma=7 / 5, eos="perfect_gas", boundaries=Dirichlet, domain_size=(1., 1.),
-                 origin=(0., 0.), cfl=0.5, maxtime=0.2, conservative=True, samples=1, _deferred=None, _arrays=None):
+                 origin=(0., 0.), cfl=0.5, maxtime=0.2, conservative=True, samples=1, gravity=(0., 0.), _deferred=None,
+                 _arrays=None):
         self.name = str(name)
+        self.gravity = bind_gravity(gravity, np.float64)
         self.gamma = _finite(gamma, "gamma")
         if eos not in EOS:
             solver_error("config", f"unknown eos {eos!r}: one of {EOS}")
@@ -271,12 +312,14 @@ class Problem:
         return cls(name, None, (), _arrays=arrays, **options)
 
     # ---- binding ---------------------------------------------------------------------------------------------------------
-    def bind(self, dX, T=np.float64, global_grid=None):
-        """This problem for a run in the data type ``T`` with cells ``dX`` on ``global_grid = (NX, NY)`` → ``BoundProblem``."""
+    def bind(self, dX, T=np.float64, global_grid=None, gravity=None):
+        """This problem for a run in the data type ``T`` with cells ``dX`` on ``global_grid = (NX, NY)`` → ``BoundProblem``.
+        ``gravity``: the run's own body force instead of the problem's (the ``gravity`` option of ``ArmonParameters``)."""
         T = np.dtype(T).type
-        key = (T, float(dX[0]), float(dX[1]), None if global_grid is None else tuple(global_grid))
+        gravity = bind_gravity(self.gravity if gravity is None else gravity, T)
+        key = (T, float(dX[0]), float(dX[1]), None if global_grid is None else tuple(global_grid), gravity)
         if key not in self._cache:
-            self._cache = {key: BoundProblem(self, dX, T, global_grid)}
+            self._cache = {key: BoundProblem(self, dX, T, global_grid, gravity)}
         return self._cache[key]
 
     def __repr__(self):
@@ -290,11 +333,13 @@ class BoundProblem:
     tag = INIT_TAG
     r = 0.
 
-    def __init__(self, problem, dX, T, global_grid):
+    def __init__(self, problem, dX, T, global_grid, gravity=(0., 0.)):
         P = self.problem = problem
+        self.gravity = bind_gravity(gravity, T)            # the two values the device receives
         self.name, self.header_name = P.name, "Problem:" + P.name
         self.gamma, self.eos, self.boundaries, self.samples = P.gamma, P.eos, P.boundaries, P.samples
-        self.domain_size, self.origin, self.cfl, self.maxtime, self.conservative = P.domain_size, P.origin, P.cfl, P.maxtime, P.conservative
+        self.domain_size, self.origin, self.cfl, self.maxtime = P.domain_size, P.origin, P.cfl, P.maxtime
+        self.conservative = P.conservative and self.gravity == (0., 0.)      # a force does work: total energy is not conserved
         self.T = T
         background, regions = P.background, P.regions
         if P._deferred is not None:
@@ -314,6 +359,8 @@ class BoundProblem:
         self.description = {"gamma": float(P.gamma).hex(), "eos": P.eos, "boundaries": list(P.boundaries), "samples": P.samples,
                             "background": hx(self.background), "regions": [[k, hx(a), hx(s)] for k, a, s in self.table],
                             "arrays": arrays_digest}
+        if self.gravity != (0., 0.):                # only then: the digests of the problems without a force stay what they were
+            self.description["gravity"] = hx(self.gravity)
         self.digest = hashlib.sha256(json.dumps(self.description, sort_keys=True).encode("utf-8")).hexdigest()
 
     def _bind_arrays(self, src, global_grid):

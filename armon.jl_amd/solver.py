@@ -684,6 +684,20 @@ def projection_remap(params, grid, axis, dt, dx):
                                               p("v"), p("E"), *w))
 
 
+def body_force(params, grid, dt):
+    """The kick that ends a cycle under a body force (``params.gravity``; DESIGN.md §4.12, the rule in include/armon_hip.h):
+    ``armon_hip_body_force`` over the real cells of ``grid``'s current state with the cycle's full step ``dt``, on the compute
+    stream. Without a force nothing is launched."""
+    if not params.forced:
+        return
+    r = _range(params, params.steps_ranges[Axis.X].real_domain)
+    gx, gy = params.gravity
+    p = grid.ptr
+    with _k(params, "body_force"):
+        check(params.fn("body_force")(params.device.ctx, r, float(dt), gx, gy, p("u") if gx != 0 else None,
+                                      p("v") if gy != 0 else None, p("E")))
+
+
 def local_time_step(params, grid):
     """ref src/reductions.jl:89-110 (dx, dy are the GLOBAL cell sizes, :92)"""
     r = _range(params, params.steps_ranges[Axis.X].real_domain)
@@ -998,7 +1012,9 @@ def solver_cycle(params, grid, last_cycle=True):
         grid.swap_state()
         fused_pair(params, grid, d_x, d_y)
         if not params.cst_dt:
-            post_dt_readback(params, grid)
+            post_dt_readback(params, grid)       # (the Y sweep's own CFL step: that of the velocities before the kick)
+        body_force(params, grid, dt)
+        if not params.cst_dt:
             if deferred:
                 gdt.update_dt(take_dt_readback(params, grid, gdt.cycle - 1))
         return False
@@ -1014,6 +1030,10 @@ def solver_cycle(params, grid, last_cycle=True):
             last = k == len(sweeps) - 1
             sweep = rank_sweep if params.use_MPI else fused_sweep
             sweep(params, grid, axis, dt, dx, emit_p=last and last_cycle, emit_dt=last and not params.cst_dt)
+            if last:
+                # the kick of a body force: after the cycle's last sweep (whose strips, if any, the compute stream has
+                # joined), before the halo of the next cycle is packed from the real cells it changes
+                body_force(params, grid, gdt.current_dt)
             if last and not last_cycle:
                 prefetch_halo(params, grid)
             if last and not params.cst_dt:
@@ -1036,6 +1056,8 @@ def solver_cycle(params, grid, last_cycle=True):
             projection_remap(params, grid, axis, dt, dx)
             if _checkpoint(params, grid, "projection_remap", axis):
                 return True
+    if not params.use_fused_sweep:
+        body_force(params, grid, gdt.current_dt)     # staged path: the same kick, after the last projection
     return False
 
 
@@ -1061,6 +1083,8 @@ def graph_cycles_usable(params):
         return False                    # and a history sample enqueued behind a cycle
     if params.state_image:
         return False                    # and an image frame rendered
+    if params.forced:
+        return False                    # and the kick of a body force enqueued behind every cycle (not part of the captured graph)
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture

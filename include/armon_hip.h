@@ -261,6 +261,30 @@ ARMON_API int armon_hip_init_regions_f32(armon_ctx*, armon_range, int64_t row_le
         const float background[4], int nregions, const armon_region_f32* regions,
         float* rho, float* u, float* v, float* E);
 
+/* Body forces (csrc/body_force.hip; no reference counterpart): a constant acceleration (gx, gy)
+ * applied as one kick at the end of every cycle. The rule, word for word:
+ * A body force is a constant acceleration (gx, gy). Each cycle ends with a kick. The kick uses that cycle's full step
+ * dt = current_dt, whatever the axis splitting and its factors. It touches every real cell and no ghost cell. It is
+ * evaluated in the data type T, one IEEE operation per operation written (the library is built with -ffp-contract=off, so
+ * no FMA appears):
+ *   hx = T(0.5) * dt * gx          hy = T(0.5) * dt * gy          (uniform, formed once per launch)
+ *   E  = E + dt * (gx * (u + hx) + gy * (v + hy))                  (u, v: the values BEFORE the kick)
+ *   u  = u + dt * gx               v  = v + dt * gy
+ * This is E += 1/2 (|u'|^2 - |u|^2) without its cancellation: the internal energy, and so p and c, do not change except by
+ * rounding. A component whose g is exactly zero is neither read for its own sake nor written: with gx == 0 the u plane is
+ * not written (a -0.0 stays -0.0) and not read (its term is left out of the sum: E = E + dt * (gy * (v + hy))); the same for
+ * gy and v. With both components zero nothing is launched. The products are formed left to right: (T(0.5) * dt) * gx.
+ * `real` is the range of the cells to kick (a block's real cells; any armon_range is walked like every staged kernel's).
+ * dt, gx, gy arrive as doubles and are rounded to T before anything else (the _f32 entry takes floats).
+ * Refused (ARMON_ERR_INVALID_ARG, before any launch, nothing written; armon_hip_last_error names the argument): a NULL ctx,
+ * an invalid range, a dt, gx or gy that is a NaN or an infinity, a NULL E when either component is non-zero, a NULL u with
+ * gx != 0, a NULL v with gy != 0 (a plane that is not touched may be NULL). Traffic per fp64 cell: one component 32 B
+ * (2 planes read, 2 written), both 48 B. Async on the context's stream. */
+ARMON_API int armon_hip_body_force(armon_ctx* ctx, armon_range real, double dt, double gx, double gy,
+        double* u, double* v, double* E);
+ARMON_API int armon_hip_body_force_f32(armon_ctx* ctx, armon_range real, float dt, float gx, float gy,
+        float* u, float* v, float* E);
+
 /* ---- in-situ reduced output (no reference counterpart: the reference writes whole fields, ref src/io.jl:2-27) ---- */
 /* Conservative coarsening of one block by the integer factors (fx, fy) >= 1. The block has rows of `row_length` elements,
  * `nghost` ghost layers and nx x ny real cells (row_length >= nx + 2 nghost); only real cells are read. Coarse cell (I, J)
@@ -1028,6 +1052,15 @@ ARMON_API int armon_hip_mgpu_drain(armon_mgpu*, const armon_tile_cycle* tiles); 
 ARMON_API int armon_hip_mgpu_drain_f32(armon_mgpu*, const armon_tile_cycle_f32* tiles);
 ARMON_API int armon_hip_mgpu_sync(armon_mgpu*);       /* host waits for the compute AND transfer streams of every local tile */
 ARMON_API int armon_hip_mgpu_set_threads(armon_mgpu*, int on);                        /* 1 / 0; < 0 = by the environment */
+/* The body force of the group's cycles (armon_hip_body_force), stored in the group: from now on every
+ * armon_hip_mgpu_cycle[_f32] ends with the kick of every local tile's real cells — dt = the sum of the plan's dt[s] over the
+ * sweeps along axis[0] (current_dt under every splitting of the reference), rounded to the run's precision like gx, gy —
+ * after the cycle's last sweep AND the join of its strips, on the tile's compute stream: behind it in stream order come
+ * the event that the packs of the exchange posted ahead wait for, so the neighbour receives kicked cells, and the next
+ * cycle's sweeps. The CFL step the last sweep emits is that of the velocities before the kick. (0, 0) = no force (the
+ * default): nothing is launched. Refused: a NULL group, a NaN or an infinity. The layouts of armon_cycle_plan,
+ * armon_tile_cycle and armon_sweep_desc do not change. */
+ARMON_API int armon_hip_mgpu_set_body_force(armon_mgpu*, double gx, double gy);
 
 /* Host-value all-reduce over the PROCESSES of the group (the conservation sums, ref src/reductions.jl:317-320);
  * op 0 = sum, 1 = min; count <= 16; synchronous; the caller folds its own local tiles first. */
