@@ -18,7 +18,7 @@ OUT_ALT = os.path.join(HERE, "libarmon_hip_alt.so")
 ALT_SOURCES = ("fused_sweep_f64.hip", "fused_sweep_f32.hip")     # the translation units the define changes
 ALT_FLAGS = ["-DARMON_ALT_KERNELS"]
 # Test infrastructure, not product: one elementwise kernel per arithmetic primitive of csrc/physics.hpp (xct::) and
-# csrc/sweep_pipeline.hpp (fused::fast::), compiled with the product's own flags so that what
+# csrc/sweep_stages.hpp (fused::fast::), compiled with the product's own flags so that what
 # tests/test_gpu_arith_primitives.py drives is what the sweeps compile. A library of its own: the exports of the two above
 # stay what include/armon_hip.h declares.
 OUT_PROBE = os.path.join(HERE, "libarmon_arith_probe.so")

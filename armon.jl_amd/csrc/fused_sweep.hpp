@@ -9,7 +9,9 @@
 //  * sweep_y_kernel.hpp: Y sweep (k_sweep_y): lane ↔ column (fp32 tuned: two adjacent columns), the register pipeline of
 //    sweep_pipeline.hpp marches along y; optional store exchange through LDS (sweep_args::y_sx).
 //  * sweep_x_kernel.hpp: X sweep, spatial form (k_sweep_x_dpp): lane ↔ cell(s) of a row, neighbours fetched with
-//    DPP wavefront shifts (sweep_spatial.hpp); no LDS, no barrier, coalesced 16-B accesses.
+//    DPP wavefront shifts (sweep_spatial.hpp, lane_shift.hpp); no LDS, no barrier, coalesced 16-B accesses.
+//  * sweep_stages.hpp: the tuned arithmetic of the seven stages of a sweep, one function per stage (fast::), with the tuned
+//    primitives rcp, rcp1, sqrt_, float2v. PipeFast and SpatialSweep::run_fast only fetch operands, call these and store.
 //  * fused_sweep_alt_kernels.hpp / fused_sweep_alt_cycle.hpp (-DARMON_ALT_KERNELS): k_sweep_x_lds, k_cycle_xy / k_cycle_pc.
 //  * placement.hip: armon_hip_tune_placement / armon_hip_choose_placement (they call armon_hip_sweep / armon_hip_sweep_pair).
 // Redundant work is confined to the LAG (≤4) cells at both ends of a run / strip. Block and strip origins are

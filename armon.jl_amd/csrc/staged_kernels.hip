@@ -8,7 +8,7 @@
 #include "common.hpp"
 #include "physics.hpp"
 #include "range_walk.hpp"
-#include "sweep_spatial.hpp"   // wavefront shifts (from_prev_lane / from_next_lane)
+#include "lane_shift.hpp"      // wavefront shifts (from_prev_lane / from_next_lane)
 
 using namespace armon;
 

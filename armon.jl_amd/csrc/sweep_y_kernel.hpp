@@ -39,7 +39,7 @@ template <class PIPE> struct y_lane<1, PIPE> {
     static __device__ __forceinline__ void track(cfl_track& t, const V& u, const V& v, const V& c) { t.add(u, v, c); }
 };
 template <class PIPE> struct y_lane<2, PIPE> {
-    // the two columns of a lane are ONE pipeline on 2-vectors: packed v_pk_* arithmetic (sweep_pipeline.hpp, float2v)
+    // the two columns of a lane are ONE pipeline on 2-vectors: packed v_pk_* arithmetic (sweep_stages.hpp, float2v)
     using V = fused::fast::float2v;
     using pipe_t = fused::PipeFast<PIPE::SCHEME, PIPE::LIM, PIPE::PROJ, PIPE::EOS, V>;
     using lds_t = float2;

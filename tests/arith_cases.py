@@ -2,7 +2,7 @@
 helper module, no fixtures).
 
 The primitives: ``xct::Den<T>::quo / quo_t / twice`` and ``xct::sqrt_`` (csrc/physics.hpp, exact flavour) and
-``fused::fast::rcp / rcp1 / sqrt_`` (csrc/sweep_pipeline.hpp, tuned flavour). Every generator is seeded and builds its operands
+``fused::fast::rcp / rcp1 / sqrt_`` (csrc/sweep_stages.hpp, tuned flavour). Every generator is seeded and builds its operands
 from integer significands and exponents, so that what a set claims (a tie, a zero remainder, a neighbour of a square) holds
 exactly. The reference is numpy's IEEE ``/`` and ``sqrt`` in the operand's precision; ``exact_quotient`` / ``exact_root`` round the
 exact value with integers alone, and tests/test_arith_cases_host.py shows the two agree on these very operands.

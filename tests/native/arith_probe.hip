@@ -8,7 +8,7 @@
 //
 // All pointers are device memory of n elements. The float2v forms take n floats, n even, as n / 2 pairs. Every entry point
 // synchronises the device before it launches and before it returns, and returns the HIP status (0 = success).
-#include "../../armon.jl_amd/csrc/sweep_pipeline.hpp"
+#include "../../armon.jl_amd/csrc/sweep_stages.hpp"
 
 using namespace armon;
 using fused::fast::float2v;
@@ -91,7 +91,7 @@ PROBE_BINARY(quo_t_f32, float, xct::Den<float>(b).quo_t(a))
 PROBE_BINARY(twice_quo_f32, float, xct::Den<float>(b).twice().quo(a))
 PROBE_UNARY(xct_sqrt_f64, double, xct::sqrt_(x))
 
-// tuned flavour (csrc/sweep_pipeline.hpp)
+// tuned flavour (csrc/sweep_stages.hpp)
 PROBE_UNARY(fast_rcp_f64, double, fused::fast::rcp(x))
 PROBE_UNARY(fast_rcp1_f64, double, fused::fast::rcp1(x))
 PROBE_UNARY(fast_sqrt_f64, double, fused::fast::sqrt_(x))

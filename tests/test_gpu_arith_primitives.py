@@ -5,7 +5,7 @@ Exact flavour (csrc/physics.hpp): ``xct::Den<T>::quo``, ``quo_t``, ``twice().quo
 division and square root — numpy's, which tests/test_arith_cases_host.py shows to be the correctly rounded values on these very
 operands — on random operands of the documented range [1e-30, 1e30], on denominators at the edges of a binade, on zero
 remainders, zero numerators of either sign, quotients within 1 ... 8 parts in 2^p of a tie, and for ``quo_t`` down through the
-subnormal range to underflow. Tuned flavour (csrc/sweep_pipeline.hpp): the error of ``fused::fast::rcp``, ``rcp1``, ``sqrt_`` is
+subnormal range to underflow. Tuned flavour (csrc/sweep_stages.hpp): the error of ``fused::fast::rcp``, ``rcp1``, ``sqrt_`` is
 measured against the exact value and held to the figure their comments state. Run with -s for the measured figures."""
 import ctypes as C
 import math
@@ -209,7 +209,7 @@ def sqrt_error(x, g, fmt):
     return worst_of(est, exact_of)
 
 
-RCP1_F64_BOUND = 2.0 ** -48 + 2.0 ** -52      # one Newton step from v_rcp_f64's 2^-24 (the figure csrc/sweep_pipeline.hpp states; the
+RCP1_F64_BOUND = 2.0 ** -48 + 2.0 ** -52      # one Newton step from v_rcp_f64's 2^-24 (the figure csrc/sweep_stages.hpp states; the
                                               # ISA guide gives none): the squared error of the start plus one rounding of the FMA
 
 

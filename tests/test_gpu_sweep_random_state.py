@@ -399,3 +399,56 @@ def test_cfl_reduction_finds_the_one_decisive_cell(blocks, dtype, axis, shape, w
     for k, piece in enumerate([(lag, n - lag), (0, lag), (n - lag, n)]):
         blk.sweep(*opts, True, dt, out_range=piece, accumulate=k > 0, cfl_sizes=cfl)
     check_outputs(blk, blk.fetch(), ref, axis)             # the three pieces together are the full sweep, bit for bit
+
+
+# ---- f. within one flavour the X sweep and the Y march are the same function ---------------------------------------------------
+
+# X on nx x ny against Y on ny x nx: three strips of 120 cells, the last partial, against eight runs of 32 rows, the last
+# partial, one column per lane; one partial strip against three workgroups of 256 columns and two runs (fp32: two columns per lane)
+TRANSPOSED_SHAPES = [(250, 9), (37, 530)]
+TRANSPOSED_OPTIONS = [("GAD", "minmod", "euler_2nd", "perfect_gas"), ("GAD", "superbee", "euler_2nd", "bizarrium"),
+                      ("Godunov", "minmod", "euler", "perfect_gas")]
+
+
+@pytest.mark.parametrize("scheme,limiter,projection,eos", TRANSPOSED_OPTIONS, ids=lambda v: v)
+@pytest.mark.parametrize("shape", TRANSPOSED_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("exact", [True, False], ids=["exact", "tuned"])
+def test_x_sweep_and_y_march_of_the_transposed_state_give_the_same_bits(blocks, exact, dtype, shape, scheme, limiter, projection,
+                                                                        eos):
+    """Within one flavour the X sweep and the Y march are the same function: the X sweep of a random state and the Y march of
+    its transpose (u and v exchanged, the same cell size along the axis, both sides mirrored with the factors (-1, +1))
+    give the same rho, u <-> v, E, p_out and c_out on every real cell, bit for bit. Tuned arithmetic: both forms call the
+    same stage functions (csrc/sweep_stages.hpp) and differ only in where an operand comes from. Exact arithmetic: both
+    state the reference's operations. (The one place where an operand order depends on the axis is the reference's
+    u^2 + v^2 of the exact EOS, and IEEE addition commutes.) Passes on the parent of the commit that added it, too: the
+    four copies of the arithmetic had not drifted."""
+    nx, ny = shape
+    g = 4
+    seed = 8000 + TRANSPOSED_SHAPES.index(shape)
+    f = state_of(nx, ny, g, eos, dtype, seed)
+    bx, by = blocks(nx, ny, g, dtype), blocks(ny, nx, g, dtype)
+    assert bx.cell_size(0) == by.cell_size(1)
+    dt = float(np.float32(rand_dt(eos, bx.cell_size(0))))
+    mirror = dict(bc=(1, 1), f_low=(-1., 1.), f_high=(-1., 1.), emit=(1, 1))
+
+    def transposed(a, shape_of_a):
+        return np.ascontiguousarray(a.reshape(shape_of_a).T).ravel()
+
+    bx.upload(f)
+    bx.mark_outputs()
+    bx.sweep(0, scheme, limiter, projection, eos, exact, dt, **mirror)
+    along_x = bx.fetch()
+    rows_x = (ny + 2 * g, nx + 2 * g)
+    by.upload({k: transposed(f[{"u": "v", "v": "u"}.get(k, k)], rows_x) for k in STATE})
+    by.mark_outputs()
+    by.sweep(1, scheme, limiter, projection, eos, exact, dt, **mirror)
+    along_y = by.fetch()
+    inside = real_mask(nx, ny, g, 0)
+    mark = MARKER[np.dtype(dtype).name]
+    for k in OUT_NAMES:
+        want = bits(along_x[k])[inside]
+        got = bits(transposed(along_y[{"u": "v", "v": "u"}.get(k, k)], rows_x[::-1]))[inside]
+        assert (want != mark).all() and (got != mark).all(), k
+        bad = np.flatnonzero(got != want)
+        assert bad.size == 0, f"{k}: {bad.size} of {want.size} real cells differ between the X sweep and the Y march"
