@@ -208,6 +208,7 @@ SIGNATURES = {
                                          C.POINTER(C.c_float * 2), _ci, C.POINTER(C.c_float * 4), _ci, C.POINTER(RegionF32)]
                                    + [_dp] * 4),
     "armon_hip_body_force": (_ci, [_vp, Range, _dbl, _dbl, _dbl] + [_dp] * 3),
+    "armon_hip_periodic_ghosts": (_ci, [_vp, _ci, _i64, _ci, _ci, _i64, _i64, _ci, C.POINTER(_dp)]),
     "armon_hip_coarsen": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 6),
     "armon_hip_derive": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 4 + [C.POINTER(DeriveSpec), _dp]),
     "armon_hip_gather_strided": (_ci, [_vp, _i64, _ci, C.POINTER(_dp), _i64, _i64, _i64, _dp]),
@@ -298,6 +299,7 @@ def _add_f32_signatures():
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
     SIGNATURES["armon_hip_derive_f32"] = SIGNATURES["armon_hip_derive"]
+    SIGNATURES["armon_hip_periodic_ghosts_f32"] = SIGNATURES["armon_hip_periodic_ghosts"]
     SIGNATURES["armon_hip_profile_f32"] = SIGNATURES["armon_hip_profile"]
     SIGNATURES["armon_hip_profile_bounds_f32"] = SIGNATURES["armon_hip_profile_bounds"]
     SIGNATURES["armon_hip_exact_norms_f32"] = SIGNATURES["armon_hip_exact_norms"]

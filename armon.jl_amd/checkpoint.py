@@ -211,6 +211,14 @@ def check_same_gravity(params, header, what):
         solver_error("config", f"{what} was written with gravity = {theirs!r}, this run has gravity = {mine!r}")
 
 
+def check_same_periodic(params, header, what):
+    """A configuration error when ``header`` and the run disagree on the periodic axes: a state under other
+    boundaries is the state of another problem."""
+    theirs, mine = list(header.get("periodic", [False, False])), [bool(v) for v in params.periodic]
+    if theirs != mine:
+        solver_error("config", f"{what} was written with periodic = {theirs!r}, this run has periodic = {mine!r}")
+
+
 def check_compatible(params, header, path):
     """A configuration error that names the first bit-deciding field on which the file and the run disagree, or a file that
     leaves nothing to run. ``nghost``, the decomposition, ``maxcycle``, ``maxtime`` and the output options are free."""

@@ -182,9 +182,13 @@ class TileGroup(NativeGroup):
     """All tiles of a ``P = (px, py)`` decomposition of one problem, in this process."""
 
     def __init__(self, P, device_ids=None, force_peer_copy=False, **options):
-        """``periodic=(x, y)`` and ``force_peer_copy`` are test aids for the transport (``armon_hip_mgpu_set_periodic``,
-        ``armon_hip_mgpu_force_peer_copy``): wrap-around neighbours, and ``hipMemcpyPeerAsync`` for every face and dt
-        scalar even though the tiles share a device."""
+        """``periodic=(x, y)``, or a problem with ``"Periodic"`` sides: the domain is periodic along that axis — the tiles'
+        neighbours wrap around (``armon_hip_mgpu_set_periodic``). ``force_peer_copy`` is a test aid for the
+        transport (``armon_hip_mgpu_force_peer_copy``): ``hipMemcpyPeerAsync`` for every face and dt scalar even though the
+        tiles share a device."""
+        from .parameters import resolve_periodic
+        self.handle = None
+        periodic = resolve_periodic(options.get("test", "Sod"), options.get("periodic"))     # (refused before anything is created)
         L = _lib.lib()
         self.P = (int(P[0]), int(P[1]))
         nt = self.P[0] * self.P[1]
@@ -193,7 +197,6 @@ class TileGroup(NativeGroup):
         self.handle = C.c_void_p()
         check(L.armon_hip_mgpu_init(self.P[0], self.P[1], (C.c_int * nt)(*ids), C.byref(self.handle)))
         self._L = L
-        periodic = tuple(bool(v) for v in options.get("periodic", (False, False)))
         if any(periodic):
             check(L.armon_hip_mgpu_set_periodic(self.handle, int(periodic[0]), int(periodic[1])))
         if force_peer_copy:

@@ -133,16 +133,19 @@ class ArmonParameters:
     # gloo in CPU tests): `use_MPI=True` needs an initialised process group, `global_comm` may carry a
     # torch ProcessGroup. Default is False here because a single process owns a single GPU.
     def _init_MPI(self, use_MPI=False, P=(1, 1), reorder_grid=True, global_comm=None, gpu_aware=True,
-                  tile_of=None, periodic=(False, False), **options):
+                  tile_of=None, periodic=None, **options):
         """``tile_of=(rank, (px, py))``: this parameter set describes ONE tile of a px×py grid whose tiles all live in
         this process (``multi_tile.TileGroup`` over ``armon_hip_mgpu_init``): same partition and neighbours as an MPI
-        rank of the reference, no process group involved. ``periodic=(x, y)``: TEST AID for the transport (the
-        reference's ``MPI.Cart_create`` is never periodic, ref src/parameters.jl:432) — neighbours wrap around along
-        that axis, so a 1×1 rank is its own neighbour and one GPU runs the real send/recv calls
-        (``armon_hip_mgpu_set_periodic``); only the library's native exchange supports it."""
+        rank of the reference, no process group involved. ``periodic=(x, y)``: the domain is periodic along that axis
+        (the reference's domain never is, ref src/parameters.jl:432). A problem with ``"Periodic"`` sides
+        sets it; given with a built-in case it overrides the case's sides on that axis. On one block the ghosts of a
+        periodic axis are filled from the block's own opposite border (``armon_hip_periodic_ghosts``; ``wrap`` records the
+        axes, the neighbours stay ``PROC_NULL``); in a tile group or a native rank the neighbours wrap around along that
+        axis (``armon_hip_mgpu_set_periodic``), so a tile can be its own neighbour; only the library's native exchange
+        supports it."""
         if tile_of is not None:
             P = tile_of[1]
-        self.periodic = (bool(periodic[0]), bool(periodic[1]))
+        self.periodic = resolve_periodic(self.test, periodic)
         if len(P) != len(self.N):
             solver_error("config", f"Mismatched dimensions: expected a grid of {len(self.N)} processes, got: {len(P)}")
         self.use_MPI = bool(use_MPI)
@@ -173,13 +176,15 @@ class ArmonParameters:
             self.cart_coords = cart_coords(self.rank, self.proc_dims)
             self.neighbours = cart_neighbours(self.cart_coords, self.proc_dims, self.periodic)
         else:
-            if any(self.periodic):
-                solver_error("config", "periodic=... needs use_MPI=true or a tile group: it describes the process grid")
             self.rank = 0
             self.proc_size = 1
             self.proc_dims = (1, 1)
             self.cart_coords = (0, 0)
             self.neighbours = {s: PROC_NULL for s in Side}
+        # the axes along which this block is its own neighbour: a lone block's periodic axes (a tile's or a rank's periodic
+        # sides have a neighbour in the topology instead)
+        lone = not self.use_MPI and tile_of is None
+        self.wrap = self.periodic if lone else (False, False)
         self.root_rank = 0
         self.is_root = self.rank == self.root_rank
         return options
@@ -377,7 +382,7 @@ class ArmonParameters:
             solver_error("config", "start_from_exact cannot be combined with restart_from: both set the initial state and the clock")
         if self.exact_solution:
             from .analytic import has_closed_form
-            if not has_closed_form(self.test):
+            if not has_closed_form(self.test, self.periodic):
                 solver_error("config", f"error_norms_step / error_norms_at_end / start_from_exact need a test case with an exact "
                                        f"solution: {self.test.name} has no closed form")
         if isinstance(history_step, bool) or not isinstance(history_step, (numbers.Integral, np.integer)) or history_step < 0:
@@ -580,6 +585,31 @@ class ArmonParameters:
                 f"P={self.proc_dims}, coords={self.cart_coords}, device_id={self.device_id})")
 
 
+def resolve_periodic(test, periodic=None):
+    """The periodic axes ``(x, y)`` of a run: ``test`` — a built-in case's name, a ``Problem`` or a bound one — gives its own
+    through ``"Periodic"`` sides (both sides of an axis together); ``periodic=None`` takes them. An explicit ``periodic``
+    overrides the sides of a test that has no periodic side of its own (a built-in case, a problem with walls or free flow);
+    against a problem that has some it must say the same, anything else is a configuration error."""
+    from .boundaries import periodic_axes
+    from .test_cases import _known
+    boundaries = _known(test)["boundaries"] if isinstance(test, str) else test.boundaries
+    own = periodic_axes(boundaries)
+    if periodic is None:
+        return own
+    try:
+        px, py = periodic
+        good = all(isinstance(v, (bool, np.bool_)) or v in (0, 1) for v in (px, py))
+    except (TypeError, ValueError):
+        good = False
+    if not good:
+        solver_error("config", f"periodic takes two booleans (x, y), got {periodic!r}")
+    given = (bool(px), bool(py))
+    if any(own) and given != own:
+        solver_error("config", f"periodic = {given} contradicts the problem's boundaries {tuple(boundaries)}, which are "
+                               f"periodic along (x, y) = {own}")
+    return given
+
+
 def cart_coords(rank, dims):
     """MPI_Cart_coords for a non-periodic row-major grid (last dimension varies fastest)."""
     return (rank // dims[1], rank % dims[1])
@@ -593,7 +623,8 @@ def cart_rank(coords, dims, periodic=(False, False)):
 
 
 def cart_neighbours(coords, dims, periodic=(False, False)):
-    """ref src/parameters.jl:441-447 (MPI.Cart_shift along dim 0 = X, dim 1 = Y); ``periodic``: test aid, see ``_init_MPI``."""
+    """ref src/parameters.jl:441-447 (MPI.Cart_shift along dim 0 = X, dim 1 = Y); ``periodic``: the axes along which the grid wraps
+    around, see ``_init_MPI``."""
     cx, cy = coords
     return {
         Side.Left: cart_rank((cx - 1, cy), dims, periodic),

@@ -24,6 +24,7 @@ import numpy as np
 
 from ._lib import Region, RegionF32, check, solver_error
 from .blocking import Axis, Side
+from .boundaries import BOUNDARY_TYPES, Periodic, periodic_axes
 from .test_cases import Dirichlet, FreeFlow, TestCase, _known, create_test
 
 HALF_PLANE, BOX, DISC, ELLIPSE = 0, 1, 2, 3        # ARMON_REGION_*
@@ -181,22 +182,39 @@ SHAPES = (HalfPlane, Box, Disc, Ellipse)
 
 
 def _boundaries(b):
+    """The four sides (left, right, bottom, top) of ``boundaries``. The constructor's one-word shorthand stays what it was —
+    ``"Dirichlet"`` or ``"FreeFlow"`` for all four sides —; periodic sides are named side by side there, so that which axes
+    wrap is written out (``all_sides`` spells one word out for the presets, which take ``"Periodic"`` alone too)."""
+    if isinstance(b, str) and b == Periodic:
+        solver_error("config", f"boundaries: '{Periodic}' is given side by side — four of '{Dirichlet}', '{FreeFlow}', '{Periodic}' "
+                               f"(left, right, bottom, top), both sides of an axis together — got {b!r} alone")
     if isinstance(b, str):
         b = (b,) * 4
     try:
         b = tuple(b)
     except TypeError:
         b = ()
-    if len(b) != 4 or not all(isinstance(s, str) and s in (FreeFlow, Dirichlet) for s in b):
-        solver_error("config", f"boundaries takes '{Dirichlet}', '{FreeFlow}' or four of them (left, right, bottom, top), got {b!r}")
+    if len(b) != 4 or not all(isinstance(s, str) and s in BOUNDARY_TYPES for s in b):
+        solver_error("config", f"boundaries takes '{Dirichlet}', '{FreeFlow}' or four of '{Dirichlet}', '{FreeFlow}', '{Periodic}' "
+                               f"(left, right, bottom, top), got {b!r}")
+    periodic_axes(b)            # both sides of an axis are periodic together
     return b
+
+
+def all_sides(b):
+    """One word of ``BOUNDARY_TYPES`` spelled out for the four sides; anything else as it is."""
+    return (b,) * 4 if isinstance(b, str) and b in BOUNDARY_TYPES else b
 
 
 class Problem:
     """A problem the solver can run: ``background`` = the ``State`` of every point no region holds, ``regions`` = a list of
     ``(shape, State)`` of which the LAST one that holds a point gives its state. ``samples``: 1, 2, 4 or 8 points per cell
     and axis; a cell whose points do not all fall in the same region takes the conservative mix of their states.
-    ``boundaries``: ``"Dirichlet"`` (a reflecting wall), ``"FreeFlow"``, or four of them (left, right, bottom, top).
+    ``boundaries``: ``"Dirichlet"`` (a reflecting wall) or ``"FreeFlow"`` for all sides, or four of ``"Dirichlet"``,
+    ``"FreeFlow"``, ``"Periodic"`` (left, right, bottom, top); the two sides of an axis are periodic together, and a problem
+    with periodic sides sets the run's ``periodic``. The presets (``like``, ``riemann``,
+    ``four_quadrants``, ``from_arrays``) also take ``"Periodic"`` alone for all four sides. The shapes of ``regions`` do not wrap around a periodic domain: a disc that leaves it on one side does
+    not come back in on the other (build such a state with several shapes, or ``from_arrays``).
     ``gravity = (gx, gy)``: a uniform body force, applied as a kick at the end of every cycle; a forced
     problem is not held to energy conservation. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
     the options of ``ArmonParameters`` override."""
@@ -240,12 +258,13 @@ class Problem:
 
     # ---- presets ---------------------------------------------------------------------------------------------------------
     @classmethod
-    def like(cls, name):
+    def like(cls, name, boundaries=None):
         """The built-in case ``name`` (Sod, Sod_y, Sod_circ, Bizarrium, Sedov) written as regions: the same constants,
-        boundaries, cfl, maxtime, domain and ``conservative`` flag, and so the same bits."""
+        boundaries, cfl, maxtime, domain and ``conservative`` flag, and so the same bits. ``boundaries``: other sides than
+        the case's own (four of them as ``Problem`` takes them, or one word for all sides, e.g. ``"Periodic"``)."""
         case = TestCase(name=name, **_known(name))
-        kw = dict(boundaries=case.boundaries, domain_size=case.domain_size, origin=case.origin, cfl=case.cfl, maxtime=case.maxtime,
-                  conservative=case.conservative, eos=case.eos)
+        kw = dict(boundaries=case.boundaries if boundaries is None else all_sides(boundaries), domain_size=case.domain_size, origin=case.origin,
+                  cfl=case.cfl, maxtime=case.maxtime, conservative=case.conservative, eos=case.eos)
         sod = (State(0.125, E=2.0), State(1., E=2.5))
         if name == "Sod":
             return cls(name, sod[0], [(HalfPlane((1, 0), 0.5), sod[1])], **kw)
@@ -272,7 +291,7 @@ class Problem:
         if axis not in ("x", "y"):
             solver_error("config", f"the axis of a Riemann problem is 'x' or 'y', got {axis!r}")
         walls = (Dirichlet, Dirichlet, FreeFlow, FreeFlow) if axis == "x" else (FreeFlow, FreeFlow, Dirichlet, Dirichlet)
-        options.setdefault("boundaries", walls)
+        options["boundaries"] = all_sides(options.get("boundaries", walls))
         return cls(name, right, [(HalfPlane((1, 0) if axis == "x" else (0, 1), at), left)], **options)
 
     @classmethod
@@ -285,7 +304,7 @@ class Problem:
             solver_error("config", f"four_quadrants takes four states, got {states!r}")
         cx, cy = _pair(centre, "the centre of the quadrants")
         inf = math.inf
-        options.setdefault("boundaries", FreeFlow)
+        options["boundaries"] = all_sides(options.get("boundaries", FreeFlow))
         return cls(name, q1, [(Box(x=(-inf, cx), y=(cy, inf)), q2), (Box(x=(-inf, cx), y=(-inf, cy)), q3),
                               (Box(x=(cx, inf), y=(-inf, cy)), q4)], **options)
 
@@ -309,6 +328,8 @@ class Problem:
         if options.get("eos") == "bizarrium" and E is None:
             solver_error("config", "with eos = 'bizarrium' the state must be given by E")
         options.pop("samples", None)
+        if "boundaries" in options:
+            options["boundaries"] = all_sides(options["boundaries"])
         return cls(name, None, (), _arrays=arrays, **options)
 
     # ---- binding ---------------------------------------------------------------------------------------------------------
@@ -384,9 +405,10 @@ class BoundProblem:
         return out, h.hexdigest()
 
     def boundary_condition(self, side):
-        """(u_factor, v_factor) for ``side``, as ``TestCase.boundary_condition``."""
+        """(u_factor, v_factor) for ``side``, as ``TestCase.boundary_condition``. A periodic side has no mirror: no kernel is
+        given its factors (the neutral pair stands in the descriptors of its sweeps, which read its ghosts instead)."""
         cond = self.boundaries[int(side) - 1]
-        if cond == FreeFlow:
+        if cond in (FreeFlow, Periodic):
             return (1., 1.)
         return (-1., 1.) if side in (Side.Left, Side.Right) else (1., -1.)
 

@@ -158,6 +158,7 @@ def pair_usable(params):
     return bool(params.use_fused_sweep and np.dtype(params.data_type).itemsize == 8 and params.axis_splitting == "Sequential"
                 and not params.use_MPI and all(n == PROC_NULL for n in params.neighbours.values())
                 and int(getattr(params, "x_kernel", 0)) == 0
+                and not params.wrap[1]        # the pair's contract: physical Y sides (an X-periodic block keeps the pair)
                 and params.block_size.n_cells * np.dtype(params.data_type).itemsize >= params.placement_min_bytes)
 
 
@@ -179,6 +180,7 @@ class BlockGrid:
         self.data = _Fields(self, FUSED_FIELDS if params.use_fused_sweep else FIELDS)
         self.alt = {f: dev.empty(n, dt_, capacity=self.pair_cells) for f in STATE_VARS} if params.use_fused_sweep else None
         self.placement = None                  # report of tune_placement (bench / tests)
+        self.pair_cycles = 0                   # host-driven cycles that went through armon_hip_sweep_pair (a report, like placement)
         self.global_dt = GlobalTimeStep(params)
         self.dt_scalar = dev.zeros(2, dt_)     # device scalar written by the fused dt reduction
         self.dt = DtReadback(params)           # deferred read-back of dt_scalar
@@ -438,11 +440,19 @@ class BlockGrid:
         vorticity, divergence) — computed on the device and reduced over the coarse cells of ``coarsen(factor)``
         (armon_hip_derive; derived.py states the rule) → dict name → ``(cny, cnx)`` array, plus ``x``, ``y`` from
         ``coarse_coordinates``. ``reduce``: ``"mean" | "max" | "min"``, or a dict quantity → name. The block is the whole
-        domain: one-sided differences at its edges, no ghost cell is read. Only the coarse planes cross PCIe."""
+        domain: one-sided differences at its edges, where no ghost cell is read; central ones across a periodic edge
+        (DESIGN.md §4.13). Only the coarse planes cross PCIe."""
         from . import derived
         from .parameters import normalize_coarsen_factor
         self.params.wait()
-        res = derived.derive_state([(self.params, self)], quantities, factor=factor, reduce=reduce, neighbours=[0])
+        # across a periodic edge the differences are central: the first ghost layer of a periodic axis is filled from the
+        # opposite border (one layer, the four state vectors) and its two sides count as sides with a neighbour
+        bits = 0
+        for axis, sides in ((Axis.X, derived.LEFT | derived.RIGHT), (Axis.Y, derived.BOTTOM | derived.TOP)):
+            if self.params.wrap[int(axis) - 1]:
+                periodic_ghosts(self.params, self, axis, STATE_VARS, layers=1)
+                bits |= sides
+        res = derived.derive_state([(self.params, self)], quantities, factor=factor, reduce=reduce, neighbours=[bits])
         res["x"], res["y"] = self.coarse_coordinates(normalize_coarsen_factor(factor))
         return res
 
@@ -628,12 +638,28 @@ def boundary_conditions(params, grid, axis, side):
                                              p("rho"), p("u"), p("v"), p("p"), p("c"), p("g"), p("E")))
 
 
+def periodic_ghosts(params, grid, axis, names, layers=None):
+    """``armon_hip_periodic_ghosts`` (the rule in include/armon_hip.h): the ghosts of ``axis`` of the vectors
+    ``names`` (at most 8) of ``grid``'s current state take the real cells of the block's opposite border, ``layers`` deep
+    (default: all ``nghost``), in one launch on the compute stream."""
+    bs = params.block_size
+    nx, ny = bs.real_size
+    vars_ = (C.c_void_p * len(names))(*[grid.data[f].ptr for f in names])
+    with _k(params, "periodic_ghosts"):
+        check(params.fn("periodic_ghosts")(params.device.ctx, 0 if axis == Axis.X else 1, bs.size[0], bs.ghosts,
+                                           bs.ghosts if layers is None else int(layers), nx, ny, len(names), vars_))
+
+
 def block_ghost_exchange(params, grid, axis):
-    """ref src/halo_exchange.jl:286-368: physical boundary → mirror BC; process boundary → exchange."""
+    """ref src/halo_exchange.jl:286-368: physical boundary → mirror BC; process boundary → exchange; a periodic axis of a lone
+    block → the ghosts of both sides from the opposite border (where the oracle's ``periodic_ghosts`` stands)."""
     remote = [s for s in sides_along(axis) if params.neighbours[s] != PROC_NULL]
     if remote:
         from .halo_exchange import exchange_sides
         exchange_sides(params, grid, axis, remote, COMM_VARS)
+    if params.wrap[int(axis) - 1]:
+        periodic_ghosts(params, grid, axis, COMM_VARS)
+        return
     for side in sides_along(axis):
         if params.neighbours[side] == PROC_NULL:
             boundary_conditions(params, grid, axis, side)
@@ -747,6 +773,9 @@ def fused_sweep(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=
     d = sweep_desc(params, grid, axis, dt, dx, emit_p, emit_c, emit_dt, out_range, dt_accumulate)
     if emit_dt and dt_out is not None:
         d.dt_cfl_out = dt_out
+    if params.wrap[int(axis) - 1]:
+        # a lone block's periodic axis: the four vectors the sweep reads get their ghosts first, on the same stream
+        periodic_ghosts(params, grid, axis, STATE_VARS)
     if ctx is not None:
         check(params.fn("sweep")(ctx, C.byref(d)))
     else:
@@ -781,8 +810,10 @@ def sweep_desc(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=F
     d.eos = 1 if params.test.eos == "bizarrium" else 0
     d.nghost = params.nghost
     lo, hi = first_side(axis), last_side(axis)
-    d.bc_low = int(params.neighbours[lo] == PROC_NULL)
-    d.bc_high = int(params.neighbours[hi] == PROC_NULL)
+    # a periodic axis of a lone block: its ghosts hold the opposite border's cells (periodic_ghosts), like a remote side's
+    wrapped = params.wrap[int(axis) - 1]
+    d.bc_low = int(params.neighbours[lo] == PROC_NULL and not wrapped)
+    d.bc_high = int(params.neighbours[hi] == PROC_NULL and not wrapped)
     d.exact = int(params.exact_arithmetic)
     d.x_kernel = int(getattr(params, "x_kernel", 0))
     d.nx, d.ny = params.N
@@ -1010,7 +1041,11 @@ def solver_cycle(params, grid, last_cycle=True):
         d_y = sweep_desc(params, grid, Axis.Y, dt * params.T(sweeps[1][1]), params.cell_size(1), emit_p=last_cycle,
                          emit_dt=not params.cst_dt)
         grid.swap_state()
+        if params.wrap[0]:
+            # X-periodic: the X ghosts of the caller's set (the plain pitch), then the pair with the X descriptor's bc_* = 0
+            periodic_ghosts(params, grid, Axis.X, STATE_VARS)
         fused_pair(params, grid, d_x, d_y)
+        grid.pair_cycles += 1
         if not params.cst_dt:
             post_dt_readback(params, grid)       # (the Y sweep's own CFL step: that of the velocities before the kick)
         body_force(params, grid, dt)
@@ -1087,7 +1122,9 @@ def graph_cycles_usable(params):
         return False                    # and the kick of a body force enqueued behind every cycle (not part of the captured graph)
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
-    if not params.device.owns_ctx:      # a tile context of a group: its stream is the group's, not ours to capture
+    if any(params.wrap):
+        return False                    # and the ghosts of a lone block's periodic axes filled before its sweeps (out of scope)
+    if not params.device.owns_ctx:     # a tile context of a group: its stream is the group's, not ours to capture
         return False
     return params.silent > 1 and params.animation_step == 0 and not params.compare and not params.kernel_callbacks
 

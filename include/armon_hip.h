@@ -285,6 +285,28 @@ ARMON_API int armon_hip_body_force(armon_ctx* ctx, armon_range real, double dt, 
 ARMON_API int armon_hip_body_force_f32(armon_ctx* ctx, armon_range real, float dt, float gx, float gy,
         float* u, float* v, float* E);
 
+/* Periodic sides (csrc/periodic.hip; the oracle's periodic_ghosts, no reference counterpart: the
+ * reference's domain is never periodic): the ghost cells of a periodic axis are filled from the opposite border of the same
+ * block, after which a sweep treats both sides of that axis as sides whose ghosts already hold neighbour data (bc_low =
+ * bc_high = 0). The rule, word for word, for each of the nvars <= 8 vectors, with cell (x, y) at
+ * (y + nghost)·row_length + x + nghost:
+ * n is the number of real cells along `axis` (nx for axis 0, ny for axis 1). Every real index k across the axis (every row
+ * for axis 0, every column for axis 1) and every l < layers is covered. Ghost -1-l takes real cell n-1-l. Ghost n+l takes
+ * real cell l.
+ * The call reads real cells only. It writes exactly the 2·layers·m ghost cells of the two sides along `axis` (m = the real
+ * cells across it) and nothing else: no corner, no real cell, no ghost of the other axis, no padding past nx + 2·nghost when
+ * row_length is larger (any row_length >= nx + 2·nghost is a valid pitch, that of armon_hip_sweep_pair's intermediate
+ * included). Values are moved, not computed: NaN payloads and signed zeros arrive as they are.
+ * `vars` is a HOST array of nvars device pointers (copied into the launch: it may be released on return).
+ * Refused (ARMON_ERR_INVALID_ARG, before any launch, nothing written; armon_hip_last_error names the argument): a NULL ctx,
+ * a NULL vars or vars[k], nvars outside 1..8, layers outside 1..nghost, n < layers, row_length < nx + 2·nghost, an axis other
+ * than 0 or 1 (and nx or ny outside 1..2^31-1). One launch for all variables and both sides, a 1-D grid with 64-bit item
+ * numbers (any number of rows). Asynchronous on the context's stream, no scratch, can be captured into a graph. */
+ARMON_API int armon_hip_periodic_ghosts(armon_ctx*, int axis, int64_t row_length, int nghost, int layers,
+        int64_t nx, int64_t ny, int nvars, double* const* vars /* HOST array of device pointers */);
+ARMON_API int armon_hip_periodic_ghosts_f32(armon_ctx*, int axis, int64_t row_length, int nghost, int layers,
+        int64_t nx, int64_t ny, int nvars, float* const* vars);
+
 /* ---- in-situ reduced output (no reference counterpart: the reference writes whole fields, ref src/io.jl:2-27) ---- */
 /* Conservative coarsening of one block by the integer factors (fx, fy) >= 1. The block has rows of `row_length` elements,
  * `nghost` ghost layers and nx x ny real cells (row_length >= nx + 2 nghost); only real cells are read. Coarse cell (I, J)
@@ -945,11 +967,13 @@ ARMON_API int armon_hip_mgpu_init_rank(int px, int py, int rank, int device_id, 
 ARMON_API int armon_hip_mgpu_prepare_rank(int px, int py, int rank, int device_id, void* stream, armon_mgpu** group);
 ARMON_API int armon_hip_mgpu_connect(armon_mgpu* group, const void* id);
 ARMON_API int armon_hip_mgpu_destroy(armon_mgpu* group);
-/* Test aids for the TRANSPORT (no reference counterpart: the reference's process grid is never periodic, ref
- * src/parameters.jl:432). _set_periodic: out-of-grid neighbours wrap around along that axis, so a 1 x 1 rank group is its
- * own neighbour on every side and ONE GPU executes the real ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd of
- * armon_hip_halo_exchange_start (call it before the first exchange; the caller's sweeps must then treat those sides as
- * remote: bc_low = bc_high = 0). _force_peer_copy: an in-process group moves its faces (and the dt scalars) with
+/* Periodic domains (no reference counterpart: the reference's process grid is never periodic, ref
+ * src/parameters.jl:432). _set_periodic: the domain is periodic along that axis — out-of-grid neighbours wrap around, so the
+ * tiles of a group or the ranks exchange across the domain's edge, and a 1 x 1 rank group is its own neighbour on every
+ * side: ONE GPU executes the real ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd of armon_hip_halo_exchange_start
+ * (call it before the first exchange; the caller's sweeps must then treat those sides as remote: bc_low = bc_high = 0).
+ * A block that belongs to no group fills the same ghosts with armon_hip_periodic_ghosts.
+ * _force_peer_copy, an aid for testing the transport: an in-process group moves its faces (and the dt scalars) with
  * hipMemcpyPeerAsync even when both tiles sit on the same device. */
 ARMON_API int armon_hip_mgpu_set_periodic(armon_mgpu* group, int periodic_x, int periodic_y);
 ARMON_API int armon_hip_mgpu_force_peer_copy(armon_mgpu* group, int on);
