@@ -207,6 +207,11 @@ SIGNATURES = {
     "armon_hip_init_regions_f32": (_ci, [_vp, Range, _i64, _ci, C.POINTER(_i64 * 2), C.POINTER(C.c_float * 2),
                                          C.POINTER(C.c_float * 2), _ci, C.POINTER(C.c_float * 4), _ci, C.POINTER(RegionF32)]
                                    + [_dp] * 4),
+    "armon_hip_init_scalar_regions": (_ci, [_vp, Range, _i64, _ci, C.POINTER(_i64 * 2), C.POINTER(_dbl * 2), C.POINTER(_dbl * 2), _ci,
+                                            C.POINTER(_dbl * 4), _ci, C.POINTER(Region)] + [_dp] * 4),
+    "armon_hip_init_scalar_regions_f32": (_ci, [_vp, Range, _i64, _ci, C.POINTER(_i64 * 2), C.POINTER(C.c_float * 2),
+                                                C.POINTER(C.c_float * 2), _ci, C.POINTER(C.c_float * 4), _ci, C.POINTER(RegionF32)]
+                                          + [_dp] * 4),
     "armon_hip_body_force": (_ci, [_vp, Range, _dbl, _dbl, _dbl] + [_dp] * 3),
     "armon_hip_periodic_ghosts": (_ci, [_vp, _ci, _i64, _ci, _ci, _i64, _i64, _ci, C.POINTER(_dp)]),
     "armon_hip_coarsen": (_ci, [_vp, _i64, _ci] + [_i64] * 4 + [_dp] * 6),
@@ -244,6 +249,7 @@ SIGNATURES = {
     "armon_hip_sweep_pair": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.c_size_t]),
     "armon_hip_choose_placement": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.POINTER(_vp), _ci,
                                          C.c_size_t, _ci, _dbl, C.POINTER(_ci * 8), C.POINTER(_dbl), C.POINTER(_ci)]),
+    "armon_hip_sweep_scalars": (_ci, [_vp, C.POINTER(SweepDesc), _ci, C.POINTER(_dp), C.POINTER(_dp)]),
     "armon_hip_mgpu_init": (_ci, [_ci, _ci, C.POINTER(_ci), C.POINTER(_vp)]),
     "armon_hip_mgpu_unique_id": (_ci, [_vp]),
     "armon_hip_mgpu_init_rank": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, C.POINTER(_vp)]),
@@ -297,6 +303,7 @@ def _add_f32_signatures():
                  "halo_exchange_finish_edge", "mgpu_edge_join", "mgpu_cycle", "mgpu_drain"):
         SIGNATURES["armon_hip_" + name + "_f32"] = SIGNATURES["armon_hip_" + name]
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
+    SIGNATURES["armon_hip_sweep_scalars_f32"] = SIGNATURES["armon_hip_sweep_scalars"]
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
     SIGNATURES["armon_hip_derive_f32"] = SIGNATURES["armon_hip_derive"]
     SIGNATURES["armon_hip_periodic_ghosts_f32"] = SIGNATURES["armon_hip_periodic_ghosts"]

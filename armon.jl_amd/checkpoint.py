@@ -4,7 +4,9 @@ counterpart: the reference's only state files are text at ``output_precision`` (
 File, in this order: the magic ``ARMONCKP``, a u32 version, a u32 header length, a UTF-8 JSON header padded with spaces to
 4096 bytes, then the dense GLOBAL planes ``[NY][NX]`` of real cells, little-endian, in the order rho, u, v, E — and ``c`` as a
 fifth plane when the run is staged (its ``next_time_step`` reads the ``c`` the last EOS of the previous cycle left). Ghost
-cells are not stored: both paths rebuild them before any read.
+cells are not stored: both paths rebuild them before any read. A fused run with passive scalars appends one
+plane ``s:<name>`` per scalar (8 planes at most) and lists the names under ``scalars`` in the header; without scalars the
+file is byte for byte what it was.
 
 The digest of plane k is the sum mod 2^64 over its cells of ``mix64(b + mix64(8 g + k + 1))`` — ``b`` the value's bit pattern
 zero-extended to 64 bits, ``g = gy NX + gx`` its global 0-based index, ``mix64`` as in ``mix64`` below. It depends on the
@@ -181,6 +183,9 @@ def _check_header(header, path):
     if "gravity" in header and not (isinstance(header["gravity"], list) and len(header["gravity"]) == 2
                                     and all(_is_hexfloat(v) for v in header["gravity"])):
         bad(f"gravity = {header['gravity']!r}")
+    if "scalars" in header and not (isinstance(header["scalars"], list) and 1 <= len(header["scalars"]) <= 4
+                                    and all(isinstance(v, str) and v and ":" not in v for v in header["scalars"])):
+        bad(f"scalars = {header['scalars']!r}")
     if ("initial_mass" in header or "initial_energy" in header) and not (
             _is_hexfloat(header.get("initial_mass")) and _is_hexfloat(header.get("initial_energy"))):
         bad("initial_mass / initial_energy")
@@ -201,6 +206,9 @@ def bit_options(params):
     gravity = tuple(getattr(test, "gravity", (0., 0.)))
     if gravity != (0., 0.):                     # a run under a body force: the headers of every other run are untouched
         options.update(gravity=[hexfloat(g) for g in gravity])
+    scalars = list(getattr(params, "scalar_names", ()))
+    if scalars:                                 # a run with passive scalars: likewise
+        options.update(scalars=scalars)
     return options
 
 
@@ -209,6 +217,14 @@ def check_same_gravity(params, header, what):
     theirs, mine = header.get("gravity", NO_GRAVITY), bit_options(params).get("gravity", NO_GRAVITY)
     if theirs != mine:
         solver_error("config", f"{what} was written with gravity = {theirs!r}, this run has gravity = {mine!r}")
+
+
+def check_same_scalars(params, header, what):
+    """A configuration error when ``header`` (a missing key = none) and the run disagree on the names of the passive scalars,
+    in plane order."""
+    theirs, mine = list(header.get("scalars", [])), list(getattr(params, "scalar_names", ()))
+    if theirs != mine:
+        solver_error("config", f"{what} was written with scalars = {theirs!r}, this run has scalars = {mine!r}")
 
 
 def check_same_periodic(params, header, what):
@@ -224,6 +240,7 @@ def check_compatible(params, header, path):
     leaves nothing to run. ``nghost``, the decomposition, ``maxcycle``, ``maxtime`` and the output options are free."""
     mine = bit_options(params)
     check_same_gravity(params, header, f"the checkpoint {path}")      # (first: a problem's digest holds its force too)
+    check_same_scalars(params, header, f"the checkpoint {path}")      # (and its scalars)
     for k in BIT_FIELDS + PROBLEM_FIELDS:
         if header.get(k) != mine.get(k):
             solver_error("config", f"the checkpoint {path} was written with {k} = {header.get(k)!r}, this run has "
@@ -238,7 +255,11 @@ def checkpoint_path(params, cycle):
 
 
 def plane_names(params):
-    return STATE_PLANES + (() if params.use_fused_sweep else ("c",))
+    """The planes of a run's checkpoint: the state, then ``s:<name>`` per passive scalar (fused path; DESIGN.md §4.14: 8
+    planes at most, hence 4 scalars), or ``c`` on the staged path."""
+    if not params.use_fused_sweep:
+        return STATE_PLANES + ("c",)
+    return STATE_PLANES + tuple("s:" + name for name in getattr(params, "scalar_names", ()))
 
 
 # ---- device side ---------------------------------------------------------------------------------------------------------

@@ -559,12 +559,14 @@ def compare_state(tiles, ref, rtol=None, atol=0.0, names=None, limit=20, band_ro
         check_comparable(p0, header["N"], header["data_type"], f"the checkpoint {ref}")
         checkpoint.check_same_gravity(p0, header, f"the checkpoint {ref}")      # a state under another body force is another problem
         checkpoint.check_same_periodic(p0, header, f"the checkpoint {ref}")     # and so is one under other boundaries
+        checkpoint.check_same_scalars(p0, header, f"the checkpoint {ref}")      # and the planes of other scalars are other fields
         theirs = tuple(header["planes"])
     else:
         header, others = None, _tiles_of(ref)
         check_comparable(p0, others[0][0].global_grid, others[0][0].data_type, "the other grid")
         checkpoint.check_same_gravity(p0, checkpoint.bit_options(others[0][0]), "the other grid")
         checkpoint.check_same_periodic(p0, checkpoint.bit_options(others[0][0]), "the other grid")
+        checkpoint.check_same_scalars(p0, checkpoint.bit_options(others[0][0]), "the other grid")
         theirs = checkpoint.plane_names(others[0][0])
     if names is None:
         names = tuple(f for f in checkpoint.plane_names(p0) if f in theirs)

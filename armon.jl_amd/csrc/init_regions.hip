@@ -91,7 +91,8 @@ k_init_regions(armon_range r, int64_t row_length, int nghost, int64_t gpos_x, in
     }
 }
 
-template <typename T, typename R>
+// SCALAR: the plane of a passive scalar in the slot of rho (armon_hip_init_scalar_regions) — any finite value, either sign
+template <typename T, typename R, bool SCALAR = false>
 int init_regions_impl(armon_ctx* ctx, armon_range r, int64_t row_length, int nghost, const int64_t global_pos[2],
                       const T origin[2], const T dX[2], int samples, const T background[4], int nregions, const R* regions,
                       T* rho, T* u, T* v, T* E)
@@ -116,7 +117,7 @@ int init_regions_impl(armon_ctx* ctx, armon_range r, int64_t row_length, int ngh
         ARMON_REQUIRE(std::isfinite(background[k]), "the background state holds a NaN or an infinity");
         tab.bg[k] = background[k];
     }
-    ARMON_REQUIRE(background[0] > 0, "the background state has rho <= 0");
+    ARMON_REQUIRE(SCALAR || background[0] > 0, "the background state has rho <= 0");
     for (int k = 0; k < nregions; k++) {
         region_t<T> g;
         memcpy(&g, &regions[k], sizeof(g));
@@ -128,7 +129,7 @@ int init_regions_impl(armon_ctx* ctx, armon_range r, int64_t row_length, int ngh
         }
         ARMON_REQUIRE(std::isfinite(g.rho) && std::isfinite(g.u) && std::isfinite(g.v) && std::isfinite(g.E),
                       "region %d: its state holds a NaN or an infinity", k);
-        ARMON_REQUIRE(g.rho > 0, "region %d: rho <= 0", k);
+        ARMON_REQUIRE(SCALAR || g.rho > 0, "region %d: rho <= 0", k);
         g.reserved = 0;
         tab.r[k] = g;
     }
@@ -158,6 +159,24 @@ int armon_hip_init_regions_f32(armon_ctx* ctx, armon_range r, int64_t row_length
 {
     return init_regions_impl<float>(ctx, r, row_length, nghost, global_pos, origin, dX, samples, background, nregions, regions,
                                     rho, u, v, E);
+}
+
+int armon_hip_init_scalar_regions(armon_ctx* ctx, armon_range r, int64_t row_length, int nghost, const int64_t global_pos[2],
+                                  const double origin[2], const double dX[2], int samples, const double background[4],
+                                  int nregions, const armon_region* regions, double* phi, double* scratch_1, double* scratch_2,
+                                  double* scratch_3)
+{
+    return init_regions_impl<double, armon_region, true>(ctx, r, row_length, nghost, global_pos, origin, dX, samples, background,
+                                                         nregions, regions, phi, scratch_1, scratch_2, scratch_3);
+}
+
+int armon_hip_init_scalar_regions_f32(armon_ctx* ctx, armon_range r, int64_t row_length, int nghost, const int64_t global_pos[2],
+                                      const float origin[2], const float dX[2], int samples, const float background[4],
+                                      int nregions, const armon_region_f32* regions, float* phi, float* scratch_1,
+                                      float* scratch_2, float* scratch_3)
+{
+    return init_regions_impl<float, armon_region_f32, true>(ctx, r, row_length, nghost, global_pos, origin, dX, samples, background,
+                                                            nregions, regions, phi, scratch_1, scratch_2, scratch_3);
 }
 
 }  // extern "C"

@@ -63,15 +63,23 @@ def reference_planes(rho, u, v, E, dx, dy, gamma):
 
 
 # ---- device side -----------------------------------------------------------------------------------------------------------
-def normalize_request(quantities, reduce="mean"):
-    """``quantities``: a name or a list of at most 8 distinct names of ``QUANTITIES``; ``reduce``: one name of ``REDUCTIONS``
-    or a dict quantity → name (``mean`` where the dict is silent) → ``(names, reductions)``."""
+SCALAR_QUANTITY = "scalar:"       # "scalar:<name>": the plane of a passive scalar, reduced like rho
+
+
+def normalize_request(quantities, reduce="mean", scalars=None):
+    """``quantities``: a name or a list of at most 8 distinct names of ``QUANTITIES`` or ``"scalar:<name>"``; ``reduce``: one
+    name of ``REDUCTIONS`` or a dict quantity → name (``mean`` where the dict is silent) → ``(names, reductions)``.
+    ``scalars``: the names of the run's passive scalars (None: any name passes here)."""
     names = (quantities,) if isinstance(quantities, str) else tuple(quantities)
     if not 1 <= len(names) <= MAX_PLANES:
         solver_error("config", f"derive takes 1 to {MAX_PLANES} quantities, got {len(names)}")
     for q in names:
+        if isinstance(q, str) and q.startswith(SCALAR_QUANTITY):
+            if scalars is not None and q[len(SCALAR_QUANTITY):] not in scalars:
+                solver_error("config", f"unknown derived quantity {q!r}: this run carries the scalars {tuple(scalars)!r}")
+            continue
         if q not in QUANTITIES:
-            solver_error("config", f"unknown derived quantity {q!r}: one of {', '.join(QUANTITIES)}")
+            solver_error("config", f"unknown derived quantity {q!r}: one of {', '.join(QUANTITIES)} or 'scalar:<name>'")
     if len(set(names)) != len(names):
         solver_error("config", f"a derived quantity may be asked for once, got {names!r}")
     if isinstance(reduce, dict):
@@ -112,7 +120,7 @@ def derive_state(tiles, quantities, factor=1, reduce="mean", neighbours=None):
     GLOBAL coarse grid. Every tile must start on a coarse-cell boundary (``check_coarsen_alignment``). ``neighbours``: per tile
     the bits to use instead of the tile's own topology. Only the coarse planes cross PCIe."""
     from .parameters import check_coarsen_alignment, coarse_shape, normalize_coarsen_factor
-    names, modes = normalize_request(quantities, reduce)
+    names, modes = normalize_request(quantities, reduce, scalars=tiles[0][0].scalar_names)
     factor = normalize_coarsen_factor(factor)
     if factor is None:
         solver_error("config", "derive needs a factor >= 1")
@@ -127,16 +135,27 @@ def derive_state(tiles, quantities, factor=1, reduce="mean", neighbours=None):
         for i, (params, grid) in enumerate(tiles):
             nx, ny = grid.size.real_size
             cnx, cny = coarse_shape((nx, ny), factor)
-            spec = _c_spec(params, names, modes, tile_neighbours(params) if neighbours is None else neighbours[i])
+            bits = tile_neighbours(params) if neighbours is None else neighbours[i]
             outs.append(params.device.empty(len(names) * cnx * cny, params.data_type))
-            check(params.fn("derive")(params.device.ctx, grid.size.size[0], grid.size.ghosts, nx, ny, fx, fy,
-                                      *[grid.ptr(f) for f in ("rho", "u", "v", "E")], C.byref(spec), C.c_void_p(outs[-1].ptr)))
+            # the flow quantities in one pass; then every scalar plane in a pass of its own, in the slot of rho with the
+            # quantity rho (no kernel of its own). `layout`: the name of each plane of the output, in its order
+            flow = [(q, m) for q, m in zip(names, modes) if not q.startswith(SCALAR_QUANTITY)]
+            passes = [(flow, "rho")] if flow else []
+            passes += [([("rho", m)], "s:" + q[len(SCALAR_QUANTITY):]) for q, m in zip(names, modes) if q.startswith(SCALAR_QUANTITY)]
+            done = 0
+            for group, rho_slot in passes:
+                spec = _c_spec(params, [q for q, _ in group], [m for _, m in group], bits)
+                dst = outs[-1].ptr + done * cnx * cny * params.data_type.itemsize
+                check(params.fn("derive")(params.device.ctx, grid.size.size[0], grid.size.ghosts, nx, ny, fx, fy,
+                                          *[grid.ptr(f) for f in (rho_slot, "u", "v", "E")], C.byref(spec), C.c_void_p(dst)))
+                done += len(group)
         for (params, grid), out in zip(tiles, outs):
             nx, ny = grid.size.real_size
             cnx, cny = coarse_shape((nx, ny), factor)
             planes = out.to_host()[:len(names) * cnx * cny].reshape(len(names), cny, cnx)
             ox, oy = (params.N_origin[0] - 1) // fx, (params.N_origin[1] - 1) // fy
-            for k, q in enumerate(names):
+            layout = [q for q in names if not q.startswith(SCALAR_QUANTITY)] + [q for q in names if q.startswith(SCALAR_QUANTITY)]
+            for k, q in enumerate(layout):
                 res[q][oy:oy + cny, ox:ox + cnx] = planes[k]
     finally:
         for out in outs:
@@ -186,7 +205,7 @@ def default_image_factor(global_grid):
 
 
 def image_path(params, quantity, cycle):
-    return os.path.join(params.output_dir, f"{params.image_file}_{quantity}_{cycle:06d}.png")
+    return os.path.join(params.output_dir, f"{params.image_file}_{quantity.replace(':', '_')}_{cycle:06d}.png")
 
 
 def image_run(owner, params, gdt):

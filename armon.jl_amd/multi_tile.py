@@ -189,6 +189,8 @@ class TileGroup(NativeGroup):
         from .parameters import resolve_periodic
         self.handle = None
         periodic = resolve_periodic(options.get("test", "Sod"), options.get("periodic"))     # (refused before anything is created)
+        if options.get("scalars") or getattr(options.get("test"), "scalars", None):
+            _lib.solver_error("config", "passive scalars are not supported for a tile group (DESIGN.md §4.14): one block only")
         L = _lib.lib()
         self.P = (int(P[0]), int(P[1]))
         nt = self.P[0] * self.P[1]

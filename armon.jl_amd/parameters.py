@@ -101,12 +101,15 @@ class ArmonParameters:
 
     # ref src/parameters.jl:632-670
     def _init_test(self, test="Sod", domain_size=None, origin=None, cfl=0., maxtime=0.,
-                   maxcycle=500_000, gravity=None, **options):
+                   maxcycle=500_000, gravity=None, scalars=None, **options):
         """``test``: the name of a built-in case, or a ``problem.Problem`` — a user-defined initial state, gamma, EOS and
         boundary types — which is bound here to the run's data type and cell size (``Problem.bind``).
         ``gravity=(gx, gy)``: a uniform body force, applied on the device as a kick at the end of every cycle (DESIGN.md
         §4.12); it overrides a problem's own, as ``domain_size`` and ``cfl`` do, and works with a built-in case too. The
-        values are rounded to the data type; ``params.test.gravity`` holds what the device receives."""
+        values are rounded to the data type; ``params.test.gravity`` holds what the device receives.
+        ``scalars``: a list of ``problem.Scalar`` (or a dict name → ``(NY, NX)`` array) — passive fields carried through the
+        fused sweeps, added after a problem's own; at most 4 in all. ``params.scalars`` holds them bound
+        to the data type, ``params.scalar_names`` their names in plane order."""
         from .problem import Problem, bind_case
         problem = test if isinstance(test, Problem) else None
         name = str(test)
@@ -119,9 +122,12 @@ class ArmonParameters:
         T = self.T
         dX = (T(self.domain_size[0]) / T(self.N[0]), T(self.domain_size[1]) / T(self.N[1]))
         if problem is not None:
-            self.test = problem.bind(dX, T, self.N, gravity=gravity)
+            self.test = problem.bind(dX, T, self.N, gravity=gravity, scalars=scalars)
         else:
-            self.test = bind_case(name, dX, T, gravity=(0., 0.) if gravity is None else gravity)
+            self.test = bind_case(name, dX, T, gravity=(0., 0.) if gravity is None else gravity, scalars=scalars,
+                                  global_grid=self.N)
+        self.scalars = tuple(self.test.scalars)
+        self.scalar_names = tuple(sc.name for sc in self.scalars)
         self.gravity = self.test.gravity
         self.forced = self.gravity != (0., 0.)
         self.maxcycle = int(maxcycle)
@@ -426,7 +432,8 @@ class ArmonParameters:
         default_reduce = {q: "max" if q == "grad_rho" else "mean" for q in names}
         if isinstance(image_reduce, dict):
             image_reduce = {**{q: m for q, m in default_reduce.items() if q not in image_reduce}, **image_reduce}
-        self.image_quantity, modes = _derived.normalize_request(names, default_reduce if image_reduce is None else image_reduce)
+        self.image_quantity, modes = _derived.normalize_request(names, default_reduce if image_reduce is None else image_reduce,
+                                                                scalars=self.scalar_names)
         self.image_reduce = dict(zip(self.image_quantity, modes))
         if image_transfer is None:
             image_transfer = {}
@@ -509,6 +516,11 @@ class ArmonParameters:
         self._device = None     # created on first use, so that configuration errors need no GPU
         # per-step dumps / comparisons need the intermediate states: only the staged path has them
         self.use_fused_sweep = bool(use_fused_sweep) and not self.compare
+        if self.scalars and not self.use_fused_sweep:
+            solver_error("config", "passive scalars are carried by the fused sweeps only: use_fused_sweep=False (the staged path, "
+                                   "which compare / is_ref select too) cannot be combined with scalars")
+        if self.scalars and self.use_MPI:
+            solver_error("config", "passive scalars are not supported for ranks of a process group (use_MPI=true): one block only")
         self.exact_arithmetic = bool(exact_arithmetic)
         self.placement_tries = int(placement_tries)
         self.placement_min_bytes = int(placement_min_bytes)     # vectors smaller than this are not worth placing

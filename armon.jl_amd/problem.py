@@ -79,17 +79,19 @@ def bind_gravity(gravity, T):
 class BoundTestCase(TestCase):
     """A built-in case bound to a run: the ``TestCase`` of ``create_test`` with the run's body force, rounded to its data type."""
     gravity: tuple = (0., 0.)
+    scalars: tuple = ()          # the run's passive scalars (BoundScalar), sampled with samples = 1
+    samples: int = 1
 
 
-def bind_case(name, dX, T, gravity=(0., 0.)):
-    """``create_test(name, dX, T)`` with the body force ``gravity`` of the run (``bind_gravity``) → ``BoundTestCase``; a forced
-    case is not ``conservative``."""
+def bind_case(name, dX, T, gravity=(0., 0.), scalars=None, global_grid=None):
+    """``create_test(name, dX, T)`` with the body force ``gravity`` of the run (``bind_gravity``) and its passive ``scalars``
+    → ``BoundTestCase``; a forced case is not ``conservative``."""
     case = create_test(name, dX, T)
     gravity = bind_gravity(gravity, T)
     kw = {f.name: getattr(case, f.name) for f in dataclasses.fields(case)}
     if gravity != (0., 0.):
         kw["conservative"] = False
-    return BoundTestCase(gravity=gravity, **kw)
+    return BoundTestCase(gravity=gravity, scalars=bind_scalars(scalars, T, global_grid), **kw)
 
 
 class State:
@@ -180,6 +182,106 @@ class Ellipse:
 
 SHAPES = (HalfPlane, Box, Disc, Ellipse)
 
+MAX_SCALARS = 4             # ARMON_MAX_SCALARS: a checkpoint holds 8 planes, 4 of them the state
+SCALAR_PREFIX = "s:"        # the plane of the scalar <name> in a checkpoint's header, and in BlockGrid.data
+
+
+class Scalar:
+    """A passive scalar φ — a dye, a mixing fraction, a species tag — carried by the flow (the rule in
+    include/armon_hip.h). ``background``: φ of every point no region holds; ``regions``: a list of ``(shape, value)`` with the
+    shapes of a ``Problem``, of which the LAST one that holds a point gives φ; a cut cell takes the volume mean of its sample
+    points (the problem's ``samples``). ``array``: φ as a global ``(NY, NX)`` array of the real cells instead. Values are any
+    finite numbers; nothing bounds φ afterwards either (a second-order remap overshoots)."""
+
+    def __init__(self, name, background=0., regions=(), array=None):
+        if not isinstance(name, str) or name == "":
+            solver_error("config", f"the name of a scalar is a non-empty string, got {name!r}")
+        if ":" in name:
+            solver_error("config", f"the name of a scalar must not contain ':', got {name!r}")
+        self.name = name
+        self.background = _finite(background, f"the background of the scalar {name!r}")
+        self.regions = list(regions)
+        if len(self.regions) > MAX_REGIONS:
+            solver_error("config", f"scalar {name!r}: {len(self.regions)} regions: at most {MAX_REGIONS} are supported")
+        for item in self.regions:
+            if not (isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], SHAPES)):
+                solver_error("config", f"scalar {name!r}: a region is a pair (shape, value), got {item!r}")
+            _finite(item[1], f"a value of the scalar {name!r}")
+        self.array = None
+        if array is not None:
+            if self.regions:
+                solver_error("config", f"scalar {name!r} takes regions or an array, not both")
+            try:
+                a = np.ascontiguousarray(array, dtype=np.float64)
+            except (TypeError, ValueError):
+                solver_error("config", f"scalar {name!r}: the array must hold numbers")
+            if a.ndim != 2:
+                solver_error("config", f"scalar {name!r} takes a 2-D array (NY, NX), got the shape {a.shape}")
+            if not np.isfinite(a).all():
+                solver_error("config", f"scalar {name!r}: the array holds a NaN or an infinity")
+            self.array = a
+
+    def __repr__(self):
+        what = "array" if self.array is not None else f"background={self.background!r}, {len(self.regions)} regions"
+        return f"Scalar({self.name!r}, {what})"
+
+
+def check_scalars(scalars):
+    """The scalars of a problem or a run as a list of ``Scalar``: a dict name → array is spelled out; at most ``MAX_SCALARS``,
+    no name twice. Anything else is a configuration error."""
+    if scalars is None:
+        return []
+    if isinstance(scalars, dict):
+        scalars = [Scalar(name, array=a) for name, a in scalars.items()]
+    try:
+        scalars = list(scalars)
+    except TypeError:
+        solver_error("config", f"scalars takes a list of Scalar (or a dict name -> array), got {scalars!r}")
+    for sc in scalars:
+        if not isinstance(sc, Scalar):
+            solver_error("config", f"scalars takes a list of Scalar (or a dict name -> array), got {sc!r}")
+    if len(scalars) > MAX_SCALARS:
+        solver_error("config", f"{len(scalars)} scalars: at most {MAX_SCALARS} are supported")
+    names = [sc.name for sc in scalars]
+    for n in names:
+        if names.count(n) > 1:
+            solver_error("config", f"the scalar {n!r} is given twice")
+    return scalars
+
+
+class BoundScalar:
+    """A ``Scalar`` in a run's data type ``T``: ``array`` (NY, NX) in ``T``, or ``background`` and ``table`` = the rows of
+    ``armon_hip_init_regions`` with the values in the slot of ρ."""
+
+    def __init__(self, scalar, T, global_grid=None):
+        self.name, self.T = scalar.name, T
+        hx = lambda vals: [float(v).hex() for v in vals]
+        with np.errstate(over="ignore"):
+            if scalar.array is not None:
+                shape = scalar.array.shape
+                if global_grid is not None and shape != (int(global_grid[1]), int(global_grid[0])):
+                    solver_error("config", f"scalar {self.name!r}: the array has the shape {shape}, the grid N = {tuple(global_grid)} "
+                                           f"needs (NY, NX) = {(int(global_grid[1]), int(global_grid[0]))}")
+                self.array = scalar.array.astype(T)
+                if not np.isfinite(self.array).all():
+                    solver_error("config", f"scalar {self.name!r} is not finite in {np.dtype(T).name}")
+                self.background, self.table = T(0), []
+                h = hashlib.sha256(repr(shape).encode())
+                h.update(np.ascontiguousarray(self.array).tobytes())
+                self.description = {"name": self.name, "array": h.hexdigest()}
+            else:
+                self.array = None
+                self.background = T(scalar.background)
+                self.table = [(shape.kind, shape.row(T), T(value)) for shape, value in scalar.regions]
+                if not all(np.isfinite(v) for v in [self.background] + [v for _, _, v in self.table]):
+                    solver_error("config", f"scalar {self.name!r} is not finite in {np.dtype(T).name}")
+                self.description = {"name": self.name, "background": float(self.background).hex(),
+                                    "regions": [[k, hx(a), float(v).hex()] for k, a, v in self.table]}
+
+
+def bind_scalars(scalars, T, global_grid=None):
+    return tuple(BoundScalar(sc, T, global_grid) for sc in check_scalars(scalars))
+
 
 def _boundaries(b):
     """The four sides (left, right, bottom, top) of ``boundaries``. The constructor's one-word shorthand stays what it was —
@@ -216,13 +318,15 @@ class Problem:
     ``four_quadrants``, ``from_arrays``) also take ``"Periodic"`` alone for all four sides. The shapes of ``regions`` do not wrap around a periodic domain: a disc that leaves it on one side does
     not come back in on the other (build such a state with several shapes, or ``from_arrays``).
     ``gravity = (gx, gy)``: a uniform body force, applied as a kick at the end of every cycle; a forced
-    problem is not held to energy conservation. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
+    problem is not held to energy conservation. ``scalars``: a list of ``Scalar`` — passive fields carried by the flow
+    (DESIGN.md §4.14); ``from_arrays`` also takes a dict name → ``(NY, NX)`` array. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
     the options of ``ArmonParameters`` override."""
 
     def __init__(self, name, background, regions=(), gamma=7 / 5, eos="perfect_gas", boundaries=Dirichlet, domain_size=(1., 1.),
-                 origin=(0., 0.), cfl=0.5, maxtime=0.2, conservative=True, samples=1, gravity=(0., 0.), _deferred=None,
+                 origin=(0., 0.), cfl=0.5, maxtime=0.2, conservative=True, samples=1, gravity=(0., 0.), scalars=(), _deferred=None,
                  _arrays=None):
         self.name = str(name)
+        self.scalars = check_scalars(scalars)
         self.gravity = bind_gravity(gravity, np.float64)
         self.gamma = _finite(gamma, "gamma")
         if eos not in EOS:
@@ -328,19 +432,27 @@ class Problem:
         if options.get("eos") == "bizarrium" and E is None:
             solver_error("config", "with eos = 'bizarrium' the state must be given by E")
         options.pop("samples", None)
+        options["scalars"] = check_scalars(options.get("scalars"))
+        for sc in options["scalars"]:
+            if sc.array is not None and sc.array.shape != np.shape(rho):
+                solver_error("config", f"from_arrays: the scalar {sc.name!r} has the shape {sc.array.shape}, the state {np.shape(rho)}")
         if "boundaries" in options:
             options["boundaries"] = all_sides(options["boundaries"])
         return cls(name, None, (), _arrays=arrays, **options)
 
     # ---- binding ---------------------------------------------------------------------------------------------------------
-    def bind(self, dX, T=np.float64, global_grid=None, gravity=None):
+    def bind(self, dX, T=np.float64, global_grid=None, gravity=None, scalars=None):
         """This problem for a run in the data type ``T`` with cells ``dX`` on ``global_grid = (NX, NY)`` → ``BoundProblem``.
-        ``gravity``: the run's own body force instead of the problem's (the ``gravity`` option of ``ArmonParameters``)."""
+        ``gravity``: the run's own body force instead of the problem's (the ``gravity`` option of ``ArmonParameters``).
+        ``scalars``: the run's own passive scalars, after the problem's (the ``scalars`` option)."""
         T = np.dtype(T).type
         gravity = bind_gravity(self.gravity if gravity is None else gravity, T)
-        key = (T, float(dX[0]), float(dX[1]), None if global_grid is None else tuple(global_grid), gravity)
+        extra = check_scalars(scalars)
+        key = (T, float(dX[0]), float(dX[1]), None if global_grid is None else tuple(global_grid), gravity,
+               tuple(id(sc) for sc in extra))
         if key not in self._cache:
-            self._cache = {key: BoundProblem(self, dX, T, global_grid, gravity)}
+            self._cache = {key: BoundProblem(self, dX, T, global_grid, gravity, check_scalars(self.scalars + extra))}
+            self._cache_scalars = extra        # (keeps the ids of the key alive)
         return self._cache[key]
 
     def __repr__(self):
@@ -354,8 +466,9 @@ class BoundProblem:
     tag = INIT_TAG
     r = 0.
 
-    def __init__(self, problem, dX, T, global_grid, gravity=(0., 0.)):
+    def __init__(self, problem, dX, T, global_grid, gravity=(0., 0.), scalars=()):
         P = self.problem = problem
+        self.scalars = bind_scalars(scalars, T, global_grid)
         self.gravity = bind_gravity(gravity, T)            # the two values the device receives
         self.name, self.header_name = P.name, "Problem:" + P.name
         self.gamma, self.eos, self.boundaries, self.samples = P.gamma, P.eos, P.boundaries, P.samples
@@ -382,6 +495,8 @@ class BoundProblem:
                             "arrays": arrays_digest}
         if self.gravity != (0., 0.):                # only then: the digests of the problems without a force stay what they were
             self.description["gravity"] = hx(self.gravity)
+        if self.scalars:                            # only then, likewise
+            self.description["scalars"] = [sc.description for sc in self.scalars]
         self.digest = hashlib.sha256(json.dumps(self.description, sort_keys=True).encode("utf-8")).hexdigest()
 
     def _bind_arrays(self, src, global_grid):
@@ -469,10 +584,38 @@ def init_state(params, grid):
                                     test.samples, C.byref(background), n, regions, p("rho"), p("u"), p("v"), p("E")))
 
 
-def _load_arrays(params, grid, arrays):
+def init_scalars(params, grid):
+    """The initial planes of the run's passive scalars. A region-built one is what
+    ``armon_hip_init_regions`` puts into ρ when the regions' densities are the scalar's values —
+    ``armon_hip_init_scalar_regions``, the same device code, with the plane in the slot of ρ and three ping-pong partners of the
+    state, which hold nothing before the first sweep, as scratch —; an array is moved in band by band like the state of ``from_arrays``."""
+    for sc in params.scalars:
+        plane = SCALAR_PREFIX + sc.name
+        if sc.array is not None:
+            _load_arrays(params, grid, {plane: sc.array}, names=(plane,))
+            continue
+        bs = params.block_size
+        full = bs.domain_range(*params.steps_ranges[Axis.X].full_domain).to_c()
+        real, Reg = (C.c_float, RegionF32) if params.data_type == np.float32 else (C.c_double, Region)
+        gpos = (C.c_int64 * 2)(params.N_origin[0] - 1, params.N_origin[1] - 1)
+        origin = (real * 2)(*params.origin)
+        dX = (real * 2)(params.cell_size(0), params.cell_size(1))
+        regions = (Reg * max(len(sc.table), 1))()
+        for reg, (kind, a, value) in zip(regions, sc.table):
+            reg.kind = kind
+            reg.a = (real * 4)(*[float(x) for x in a])
+            reg.rho, reg.u, reg.v, reg.E = float(value), 0., 0., 0.
+        background = (real * 4)(float(sc.background), 0., 0., 0.)
+        scratch = [C.c_void_p(grid.alt[f].ptr) for f in ("u", "v", "E")]
+        check(params.fn("init_scalar_regions")(params.device.ctx, full, bs.size[0], bs.ghosts, C.byref(gpos), C.byref(origin),
+                                               C.byref(dX), int(getattr(params.test, "samples", 1)), C.byref(background),
+                                               len(sc.table), regions, grid.ptr(plane), *scratch))
+
+
+def _load_arrays(params, grid, arrays, names=None):
     """The tile's window of the global arrays, band by band, through ``armon_hip_state_unpack`` (what ``load_state`` uses)."""
     from . import checkpoint
-    names = checkpoint.STATE_PLANES
+    names = checkpoint.STATE_PLANES if names is None else names
     nx = params.N[0]
     ox, oy = params.N_origin[0] - 1, params.N_origin[1] - 1
     dev = params.device

@@ -17,6 +17,7 @@ from . import _lib
 from ._lib import BlockDataPtrs, FIELDS, SweepDesc, check, solver_error
 from .blocking import Axis, Side, first_side, last_side, sides_along
 from .parameters import LIMITERS, PROC_NULL, PROJECTIONS, SCHEMES
+from .problem import SCALAR_PREFIX
 
 MAIN_VARS = ("x", "y", "rho", "u", "v", "E", "p", "c", "g", "us", "ps")   # ref src/blocking/blocks.jl:47
 SAVED_VARS = ("x", "y", "rho", "u", "v", "p")                              # ref :49
@@ -40,6 +41,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     error_norms: list = field(default_factory=list)     # (cycle, time, analytic.ErrorNorms or None: no solution at that time) of error_norms_step / error_norms_at_end
     history: object = None                               # history.History of history_step
     images: list = field(default_factory=list)          # paths of the frames of image_step / image_at_end
+    scalars: tuple = ()                                  # names of the run's passive scalars (read with stats.data.scalar(name))
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -156,6 +158,7 @@ def pair_usable(params):
     (``placement_min_bytes`` per vector: smaller ones gain nothing from either and keep the plain layout). Decided once per block (its vectors are allocated with room for that layout); ``pair_cycle``
     decides cycle by cycle."""
     return bool(params.use_fused_sweep and np.dtype(params.data_type).itemsize == 8 and params.axis_splitting == "Sequential"
+                and not params.scalar_names   # the scalar sweep reads the pre-sweep state: the pair's Y sweep overwrites the pre-X one
                 and not params.use_MPI and all(n == PROC_NULL for n in params.neighbours.values())
                 and int(getattr(params, "x_kernel", 0)) == 0
                 and not params.wrap[1]        # the pair's contract: physical Y sides (an X-periodic block keeps the pair)
@@ -179,6 +182,11 @@ class BlockGrid:
         self.pair_cells = self.size.line_cells(np.dtype(dt_).itemsize) if pair_usable(params) else None
         self.data = _Fields(self, FUSED_FIELDS if params.use_fused_sweep else FIELDS)
         self.alt = {f: dev.empty(n, dt_, capacity=self.pair_cells) for f in STATE_VARS} if params.use_fused_sweep else None
+        # passive scalars: plane "s:<name>" and its ping-pong partner, 2·ns more vectors; none without scalars
+        self.scalar_planes = tuple(SCALAR_PREFIX + name for name in params.scalar_names)
+        for f in self.scalar_planes:
+            self.data[f] = dev.zeros(n, dt_)
+            self.alt[f] = dev.zeros(n, dt_)
         self.placement = None                  # report of tune_placement (bench / tests)
         self.pair_cycles = 0                   # host-driven cycles that went through armon_hip_sweep_pair (a report, like placement)
         self.global_dt = GlobalTimeStep(params)
@@ -217,6 +225,18 @@ class BlockGrid:
         """After a fused sweep the fresh state lives in ``alt``: exchange the roles."""
         for f in STATE_VARS:
             self.data[f], self.alt[f] = self.alt[f], self.data[f]
+
+    def swap_scalars(self):
+        """After a scalar sweep the fresh planes live in ``alt``: exchange the roles."""
+        for f in self.scalar_planes:
+            self.data[f], self.alt[f] = self.alt[f], self.data[f]
+
+    def scalar(self, name):
+        """The real cells of the passive scalar ``name`` on the host → ``(ny, nx)`` array."""
+        if name not in self.params.scalar_names:
+            solver_error("config", f"no scalar {name!r}: this run carries {self.params.scalar_names}")
+        self.params.wait()
+        return self.real_view(self.data[SCALAR_PREFIX + name].to_host()).copy()
 
     def tune_placement(self, min_bytes=None, spare=None, keep_state=True):
         """Pick a good PHYSICAL placement for the 8 vectors a fused sweep streams (4 read + 4 written).
@@ -490,7 +510,7 @@ class BlockGrid:
         n = self.size.n_cells * np.dtype(self.params.data_type).itemsize
         # (+ the padding of the 8 state vectors that hold the line-pitched intermediate of armon_hip_sweep_pair)
         pad = sum(v.capacity_bytes - v.nbytes for v in list(self.data.values()) + (list(self.alt.values()) if self.alt else []))
-        return n * (len(self.data) + (4 if self.alt else 0)) + pad
+        return n * (len(self.data) + (len(self.alt) if self.alt else 0)) + pad
 
 
 # ---- per-block kernel wrappers -----------------------------------------------------------------
@@ -532,6 +552,9 @@ def init_test(params, grid, tune=True):
         else:
             tune_staged_placement(params, grid)
     _init_test_kernel(params, grid)
+    if grid.scalar_planes:
+        from .problem import init_scalars
+        init_scalars(params, grid)
     grid.initialised = True
 
 
@@ -781,8 +804,24 @@ def fused_sweep(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=
     else:
         with _k(params, "sweep_x" if axis == Axis.X else "sweep_y"):
             check(params.fn("sweep")(params.device.ctx, C.byref(d)))
+        if grid.scalar_planes:
+            scalar_sweep(params, grid, axis, d)
     if swap:
         grid.swap_state()
+
+
+def scalar_sweep(params, grid, axis, d):
+    """The passive scalars through the sweep ``d`` describes (``armon_hip_sweep_scalars``): enqueued behind
+    ``armon_hip_sweep(d)``, whose input — the pre-sweep state — is still intact, and before ``swap_state``; then the planes'
+    own ping-pong partners take their place. On a periodic axis the planes get their ghosts first, like the state."""
+    if params.wrap[int(axis) - 1]:
+        periodic_ghosts(params, grid, axis, grid.scalar_planes)
+    ns = len(grid.scalar_planes)
+    phi_in = (C.c_void_p * ns)(*[grid.data[f].ptr for f in grid.scalar_planes])
+    phi_out = (C.c_void_p * ns)(*[grid.alt[f].ptr for f in grid.scalar_planes])
+    with _k(params, "scalars_x" if axis == Axis.X else "scalars_y"):
+        check(params.fn("sweep_scalars")(params.device.ctx, C.byref(d), ns, phi_in, phi_out))
+    grid.swap_scalars()
 
 
 def pair_cycle(params, grid):
@@ -1120,6 +1159,8 @@ def graph_cycles_usable(params):
         return False                    # and an image frame rendered
     if params.forced:
         return False                    # and the kick of a body force enqueued behind every cycle (not part of the captured graph)
+    if params.scalar_names:
+        return False                    # and the scalar sweep enqueued behind every sweep (host-driven only)
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
         return False
     if any(params.wrap):
@@ -1457,6 +1498,7 @@ def armon(params):
     stats.error_norms = list(grid.error_norms_taken)
     stats.history = grid.history
     stats.images = list(grid.images)
+    stats.scalars = tuple(params.scalar_names)
     if params.return_data:
         stats.data = grid
     return stats

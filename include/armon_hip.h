@@ -935,6 +935,54 @@ ARMON_API int armon_hip_choose_placement_f32(armon_ctx*, const armon_sweep_desc_
         void* const* pool, int n_pool, size_t bytes, int tries, double tolerance, int picks[8], double* times_ms,
         int* tries_done);
 
+/* ---- passive scalars: advected fields carried through a fused sweep --------------------------------- */
+/* No reference counterpart. The rule:
+ * - Up to ARMON_MAX_SCALARS = 4 planes φ_k, in the layout of the state vectors: flat, ghosted, plain pitch nx + 2·nghost.
+ * - For every directional sweep of the state, the scalar sweep uses the same axis, dt, dx, scheme, limiter, projection, EOS,
+ *   `exact` flag and bc_low / bc_high. It computes, from the pre-sweep state and the pre-sweep φ_k, exactly what that sweep
+ *   computes for its transverse velocity, with φ_k in place of `ut` everywhere except the EOS:
+ *   - Lagrangian phase: φ unchanged.
+ *   - q = ρ_lag·φ.
+ *   - Limited slope, first or second order.
+ *   - Advection flux from the upwind donor.
+ *   - φ' = T_q / T_ρ.
+ * - Use the same IEEE operations in the same order as the flavour in use:
+ *   - Exact: the formulas of Pipe / run_exact.
+ *   - Tuned: the fast:: stage functions.
+ * - On a side with bc = 1, the ghost φ is the mirrored real cell with factor +1, whatever the velocity factors. This is the
+ *   transverse factor of every case and every boundary type here.
+ * - With bc = 0 the ghosts of φ are read as they are.
+ * - The scalar sweep writes the real cells of phi_out[k] and nothing else. It leaves alone:
+ *   - ghost cells and pitch padding;
+ *   - phi_in;
+ *   - all eight state arrays of the descriptor.
+ *
+ * armon_hip_sweep_scalars: one launch for all `ns` planes, on the context's stream. The fused sweeps are out of place, so the
+ * call follows armon_hip_sweep with that sweep's own descriptor, before the caller swaps its ping-pong arrays. Read from the
+ * descriptor: the pre-sweep state rho_in, u_in, v_in, E_in and the scalars (axis .. gamma, the mirror flags and factors);
+ * ignored: rho_out .. E_out, p_out, c_out, dt_cfl_out and what goes with it. phi_in / phi_out: HOST arrays of `ns` device
+ * pointers, copied into the launch. Traffic: (32 + 16·ns) B per fp64 cell. Refused before any launch (ARMON_ERR_INVALID_ARG,
+ * armon_hip_last_error names the argument): ns outside 1..ARMON_MAX_SCALARS; a NULL plane; a phi_out[k] that is a phi_in, another
+ * phi_out or a state array of the descriptor; dt_state != NULL (host-driven only); a partial piece (out_lo / out_hi not the
+ * whole block); x_kernel != 0; and everything armon_hip_sweep refuses (tags, empty or oversized blocks, nghost below the
+ * stencil's reach, mirror factors other than +1 / -1, a NULL rho_in .. E_in). */
+#define ARMON_MAX_SCALARS 4
+/* The initial plane of a region-built scalar: armon_hip_init_regions (same arguments, same device code, same rule) with the
+ * scalar's values where the regions' densities stand — rho of `background` and of every region; their u, v, E are not used —
+ * and `phi` where rho stands: bit for bit the rho plane of that call (the last region that holds a point wins; a cut cell
+ * takes the mean of its samples). Values are any finite numbers, zero and negative ones included. scratch_1..3: three
+ * planes of the same size whose content is lost. */
+ARMON_API int armon_hip_init_scalar_regions(armon_ctx*, armon_range, int64_t row_length, int nghost, const int64_t global_pos[2],
+        const double origin[2], const double dX[2], int samples, const double background[4], int nregions,
+        const armon_region* regions, double* phi, double* scratch_1, double* scratch_2, double* scratch_3);
+ARMON_API int armon_hip_init_scalar_regions_f32(armon_ctx*, armon_range, int64_t row_length, int nghost, const int64_t global_pos[2],
+        const float origin[2], const float dX[2], int samples, const float background[4], int nregions,
+        const armon_region_f32* regions, float* phi, float* scratch_1, float* scratch_2, float* scratch_3);
+ARMON_API int armon_hip_sweep_scalars(armon_ctx*, const armon_sweep_desc*, int ns, const double* const* phi_in,
+                                      double* const* phi_out);
+ARMON_API int armon_hip_sweep_scalars_f32(armon_ctx*, const armon_sweep_desc_f32*, int ns, const float* const* phi_in,
+                                          float* const* phi_out);
+
 
 /* ---- multi-GPU: tile-decomposed grid, halo exchange and dt reduction on the device ------------------------------ */
 /* Replaces the reference's MPI path: start_exchange / finish_exchange (ref src/halo_exchange.jl:229-283), the side
