@@ -1,6 +1,7 @@
 """What the fused-sweep tests share (test infrastructure: a plain helper module, no tests): a block on the device whose sweep
 options are set launch by launch, the marker every output array starts from, the cell-by-cell check of what a sweep wrote, and
-the launch forms of the tuned kernels. Used by tests/test_gpu_sweep_random_state.py and tests/test_gpu_special_states.py."""
+the launch forms of the tuned kernels. Used by tests/test_gpu_sweep_random_state.py, tests/test_gpu_special_states.py and the
+scalar-sweep tests (tests/scalars_harness.py)."""
 import ctypes as C
 
 import numpy as np
@@ -29,11 +30,11 @@ def bits(a):
 class Block:
     """A BlockGrid of one shape, ghost width and precision; the sweep's options are set on the descriptor, launch by launch."""
 
-    def __init__(self, dev, nx, ny, g, dtype):
+    def __init__(self, dev, nx, ny, g, dtype, **params):
         import armon_amd
         from armon_amd.solver import BlockGrid
         self.nx, self.ny, self.g, self.dtype = nx, ny, g, np.dtype(dtype)
-        self.params = armon_amd.ArmonParameters(test="Sod", N=(nx, ny), nghost=g, data_type=dtype, silent=5, ctx=dev.ctx)
+        self.params = armon_amd.ArmonParameters(test="Sod", N=(nx, ny), nghost=g, data_type=dtype, silent=5, ctx=dev.ctx, **params)
         self.dev = self.params.device
         self.grid = BlockGrid(self.params)
         self.n = (nx + 2 * g) * (ny + 2 * g)
@@ -84,16 +85,17 @@ class Block:
 
 
 def block_cache():
-    """Generator behind a module-scoped fixture: yields get(nx, ny, g, dtype) -> Block, one context for all of them."""
+    """Generator behind a module-scoped fixture: yields get(nx, ny, g, dtype) -> Block, one context for all of them. Keywords
+    go to the block's ArmonParameters (a ghost width below 4 needs the scheme and projection that allow it)."""
     import armon_amd
     from armon_amd.device import HIPDevice
     dev = HIPDevice(0)
     cache = {}
 
-    def get(nx, ny, g, dtype):
-        key = (nx, ny, g, np.dtype(dtype).name)
+    def get(nx, ny, g, dtype, **params):
+        key = (nx, ny, g, np.dtype(dtype).name) + tuple(sorted(params.items()))
         if key not in cache:
-            cache[key] = Block(dev, nx, ny, g, dtype)
+            cache[key] = Block(dev, nx, ny, g, dtype, **params)
         return cache[key]
 
     yield get

@@ -131,6 +131,30 @@ def test_a_block_of_more_rows_than_a_grid_extent_is_one_launch(dev, axis, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("axis", [0, 1], ids=["x", "y"])
+def test_a_block_of_more_spans_than_the_grid_holds_waves_is_one_launch(dev, axis, dtype):
+    """The wide twin: along y, 2 variables x 8 rows x 2344 spans of a wave (1172 in fp32) are at least twice as many wave items as a grid
+    capped at 8 workgroups of 4 waves per CU holds waves, on any device of up to 293 CUs: every wave of k_periodic_y goes round
+    its grid-stride loop a second time (on 256 CUs: 8192 waves, 37504 and 18752 items); along x, the two lines are 300007 cells apart."""
+    nx, ny, g, nvars = 300007, 5, 4, 2
+    pitch = nx + 2 * g
+    size = pitch * (ny + 2 * g)
+    host = [marked(size, dtype, 130003 * k) for k in range(nvars)]
+    d = [dev.from_host(h) for h in host]
+    try:
+        assert call_wrap(dev, dtype, axis, pitch, g, g, nx, ny, [a.ptr for a in d]) == 0, dev._L.armon_hip_last_error()
+        dev.wait()
+        for a, h in zip(d, host):
+            want, mask = restated(h, axis, pitch, g, g, nx, ny)
+            got = a.to_host()
+            assert np.array_equal(bits(got), bits(want))
+            assert (bits(got)[mask] != bits(h)[mask]).all()                                  # every ghost was written
+    finally:
+        for a in d:
+            a.free()
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_the_wrap_refuses_before_any_launch(dev, dtype):
     nx, ny, g = 6, 3, 4
     pitch = nx + 2 * g

@@ -8,17 +8,16 @@ workgroup, a partial last one, an odd pitch; Y (530, 37), (70, 101): more than o
 ones; and the smallest block the state sweep accepts (LAG x LAG cells, tests/test_gpu_random_shapes.py). The mirror factors
 of the harness have a transverse factor of -1 on the high side: the planes are mirrored with +1 all the same.
 Tuned arithmetic prints what it measures (pytest -s)."""
-import ctypes as C
-import functools
 import os
 import random
 
 import numpy as np
 import pytest
 
+from scalars_harness import Planes, assert_untouched, case_numbers, descriptor, kappa_of_plane, lag_of, launch, rand_planes
 from scalars_restated import restated_sweep, run_cycles
-from sweep_harness import F_HIGH, F_LOW, MARKER, TAGS, bits, block_cache
-from sweep_reference import STATE, rand_dt, rand_state, real_mask, uv_factors
+from sweep_harness import F_HIGH, F_LOW, MARKER, bits, block_cache
+from sweep_reference import STATE, rand_state, real_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -39,84 +38,12 @@ def A():
     return armon_amd
 
 
-def lag_of(scheme, projection):
-    return 2 + (scheme == "GAD") + (projection == "euler_2nd")
-
-
 @pytest.fixture(scope="module")
 def blocks():
     yield from block_cache()
 
 
 # ---- one sweep through the C ABI -----------------------------------------------------------------------------------------
-
-class Planes:
-    """``ns`` input planes and ``ns`` output planes on the device of a harness block."""
-
-    def __init__(self, blk, ns):
-        self.blk, self.ns = blk, ns
-        self.inp = [blk.dev.empty(blk.n, blk.dtype) for _ in range(ns)]
-        self.out = [blk.dev.empty(blk.n, blk.dtype) for _ in range(ns)]
-
-    def upload(self, planes):
-        for a, h in zip(self.inp, planes):
-            a.copy_from_host(h)
-        for a in self.out:
-            a.copy_from_host(self.blk.marker)
-
-    def fetch(self):
-        self.blk.dev.wait()
-        return [a.to_host() for a in self.inp], [a.to_host() for a in self.out]
-
-    def free(self):
-        self.blk.dev.wait()
-        for a in self.inp + self.out:
-            a.free()
-
-
-def descriptor(blk, axis, scheme, limiter, projection, eos, exact, dt, bc=(1, 1), f_low=F_LOW, f_high=F_HIGH):
-    from armon_amd.blocking import Axis
-    from armon_amd.solver import sweep_desc
-    d = sweep_desc(blk.params, blk.grid, Axis.X if axis == 0 else Axis.Y, dt, blk.cell_size(axis), emit_p=True, emit_c=True, emit_dt=True)
-    d.scheme, d.limiter = TAGS["scheme"][scheme], TAGS["limiter"][limiter]
-    d.projection, d.eos, d.exact = TAGS["projection"][projection], TAGS["eos"][eos], int(exact)
-    d.bc_low, d.bc_high = bc
-    d.u_factor_low, d.v_factor_low = uv_factors(axis, f_low)
-    d.u_factor_high, d.v_factor_high = uv_factors(axis, f_high)
-    return d
-
-
-def launch(blk, d, inp, out, ns=None, expect=0):
-    ns = len(inp) if ns is None else ns
-    a = (C.c_void_p * max(len(inp), 1))(*[x.ptr if x is not None else None for x in inp])
-    b = (C.c_void_p * max(len(out), 1))(*[x.ptr if x is not None else None for x in out])
-    rc = blk.params.fn("sweep_scalars")(blk.dev.ctx, C.byref(d), ns, a, b)
-    msg = blk.dev._L.armon_hip_last_error().decode()
-    assert (rc == 0) == (expect == 0) and (expect == 0 or rc == expect), (rc, msg)
-    return msg
-
-
-def rand_planes(nx, ny, g, ns, dtype, seed):
-    rng = np.random.default_rng(seed)
-    return [rng.uniform(-1., 2., (nx + 2 * g) * (ny + 2 * g)).astype(dtype) for _ in range(ns)]
-
-
-def case_numbers(nx, ny, axis, eos, dtype):
-    T = np.dtype(dtype).type
-    cs = [float(T(1.) / T(nx)), float(T(1.) / T(ny))]            # ArmonParameters.cell_size of the unit square
-    return float(np.float32(rand_dt(eos, cs[axis]))), cs[axis]
-
-
-def assert_untouched(blk, f, what):
-    """The eight state arrays of the descriptor, p, c and the dt scalar after a scalar sweep: the input as uploaded, the marker."""
-    mark = MARKER[blk.dtype.name]
-    host = blk.grid.device_to_host(STATE)
-    for k in STATE:
-        assert np.array_equal(bits(host[k]), bits(f[k])), f"{what}: the state's {k} was modified"
-    out = blk.fetch()
-    for k, a in out.items():
-        assert (bits(a) == mark).all(), f"{what}: {k} of the descriptor's outputs was written"
-
 
 def draw_cases(seed):
     rng = random.Random(seed)
@@ -201,25 +128,6 @@ TUNED_CASES = [(dtype, axis, shape, scheme, limiter, projection, eos, g)
                    (0, (250, 9), "GAD", "minmod", "euler_2nd", "perfect_gas", 4), (0, (123, 5), "Godunov", "minmod", "euler", "bizarrium", 5),
                    (1, (530, 37), "GAD", "minmod", "euler_2nd", "perfect_gas", 4), (1, (70, 101), "GAD", "superbee", "euler", "bizarrium", 5),
                    (0, (123, 5), "GAD", "no_limiter", "euler_2nd", "bizarrium", 4), (1, (70, 101), "Godunov", "minmod", "euler_2nd", "perfect_gas", 4)]]
-
-
-@functools.lru_cache(maxsize=None)
-def kappa_of_plane(nx, ny, g, axis, scheme, limiter, projection, eos, seed):
-    """As kappa_of of tests/test_gpu_sweep_random_state.py, for the planes: max|restated32 - restated64| / (eps32 max|restated64|)
-    over the real cells, both restatements on the SAME numbers — state, planes, cell size and step rounded to fp32. Returns
-    (kappa per plane, the fp64 restatement of those fp32 inputs)."""
-    f32 = rand_state(nx, ny, g, eos, "float32", seed)
-    planes32 = rand_planes(nx, ny, g, 2, "float32", seed + 1)
-    dt, dx = case_numbers(nx, ny, axis, eos, "float32")
-    opts = (nx, ny, g, axis, scheme, limiter, projection, eos, dt, dx, 1, 1, F_LOW, F_HIGH)
-    o32, _ = restated_sweep(f32, planes32, *opts, "float32")
-    o64, _ = restated_sweep({k: a.astype(np.float64) for k, a in f32.items()}, [p.astype(np.float64) for p in planes32], *opts, "float64")
-    inside = real_mask(nx, ny, g, axis)
-    eps32 = float(np.finfo(np.float32).eps)
-    kappa = [float(np.abs(a32[inside].astype(np.float64) - a64[inside]).max() / (eps32 * np.abs(a64[inside]).max()))
-             for a32, a64 in zip(o32, o64)]
-    assert all(k > 0.5 for k in kappa), kappa              # a yardstick, not an accident of one cell
-    return kappa
 
 
 @pytest.mark.parametrize("dtype,axis,shape,scheme,limiter,projection,eos,g", TUNED_CASES,
