@@ -134,6 +134,17 @@ class RegionF32(C.Structure):
                 ("rho", C.c_float), ("u", C.c_float), ("v", C.c_float), ("E", C.c_float)]
 
 
+class DiffuseDesc(C.Structure):
+    """armon_diffuse_desc(_f32) — one step of physical diffusion (include/armon_hip.h, armon_hip_diffuse)."""
+    _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("ns", C.c_int32), ("periodic", C.c_int32 * 4),
+                ("u_factor", C.c_double * 4), ("v_factor", C.c_double * 4),
+                ("dt", C.c_double), ("dx", C.c_double), ("dy", C.c_double), ("nu", C.c_double), ("chi", C.c_double),
+                ("D", C.c_double * 4),
+                ("rho", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("E", C.c_void_p),
+                ("rho_out", C.c_void_p), ("u_out", C.c_void_p), ("v_out", C.c_void_p), ("E_out", C.c_void_p),
+                ("phi", C.c_void_p * 4), ("phi_out", C.c_void_p * 4)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -250,6 +261,7 @@ SIGNATURES = {
     "armon_hip_choose_placement": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.POINTER(_vp), _ci,
                                          C.c_size_t, _ci, _dbl, C.POINTER(_ci * 8), C.POINTER(_dbl), C.POINTER(_ci)]),
     "armon_hip_sweep_scalars": (_ci, [_vp, C.POINTER(SweepDesc), _ci, C.POINTER(_dp), C.POINTER(_dp)]),
+    "armon_hip_diffuse": (_ci, [_vp, C.POINTER(DiffuseDesc)]),
     "armon_hip_mgpu_init": (_ci, [_ci, _ci, C.POINTER(_ci), C.POINTER(_vp)]),
     "armon_hip_mgpu_unique_id": (_ci, [_vp]),
     "armon_hip_mgpu_init_rank": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, C.POINTER(_vp)]),
@@ -304,6 +316,7 @@ def _add_f32_signatures():
         SIGNATURES["armon_hip_" + name + "_f32"] = SIGNATURES["armon_hip_" + name]
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
     SIGNATURES["armon_hip_sweep_scalars_f32"] = SIGNATURES["armon_hip_sweep_scalars"]
+    SIGNATURES["armon_hip_diffuse_f32"] = SIGNATURES["armon_hip_diffuse"]
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
     SIGNATURES["armon_hip_derive_f32"] = SIGNATURES["armon_hip_derive"]
     SIGNATURES["armon_hip_periodic_ghosts_f32"] = SIGNATURES["armon_hip_periodic_ghosts"]

@@ -186,6 +186,11 @@ def _check_header(header, path):
     if "scalars" in header and not (isinstance(header["scalars"], list) and 1 <= len(header["scalars"]) <= 4
                                     and all(isinstance(v, str) and v and ":" not in v for v in header["scalars"])):
         bad(f"scalars = {header['scalars']!r}")
+    if "diffusion" in header:
+        d = header["diffusion"]
+        if not (isinstance(d, dict) and _is_hexfloat(d.get("nu")) and _is_hexfloat(d.get("chi")) and isinstance(d.get("scalars"), dict)
+                and all(isinstance(k, str) and _is_hexfloat(v) for k, v in d["scalars"].items())):
+            bad(f"diffusion = {d!r}")
     if ("initial_mass" in header or "initial_energy" in header) and not (
             _is_hexfloat(header.get("initial_mass")) and _is_hexfloat(header.get("initial_energy"))):
         bad("initial_mass / initial_energy")
@@ -209,7 +214,18 @@ def bit_options(params):
     scalars = list(getattr(params, "scalar_names", ()))
     if scalars:                                 # a run with passive scalars: likewise
         options.update(scalars=scalars)
+    if getattr(params, "diffusive", False):     # a run with physical diffusion: likewise
+        from .problem import diffusion_description
+        options.update(diffusion=diffusion_description(params.viscosity, params.heat_diffusivity, params.scalars))
     return options
+
+
+def check_same_diffusion(params, header, what):
+    """A configuration error when ``header`` (a missing key = nothing diffuses) and the run disagree on the coefficients of
+    the physical diffusion: a state under other coefficients is the state of another problem."""
+    theirs, mine = header.get("diffusion"), bit_options(params).get("diffusion")
+    if theirs != mine:
+        solver_error("config", f"{what} was written with diffusion = {theirs!r}, this run has diffusion = {mine!r}")
 
 
 def check_same_gravity(params, header, what):
@@ -241,6 +257,7 @@ def check_compatible(params, header, path):
     mine = bit_options(params)
     check_same_gravity(params, header, f"the checkpoint {path}")      # (first: a problem's digest holds its force too)
     check_same_scalars(params, header, f"the checkpoint {path}")      # (and its scalars)
+    check_same_diffusion(params, header, f"the checkpoint {path}")    # (and its diffusion coefficients)
     for k in BIT_FIELDS + PROBLEM_FIELDS:
         if header.get(k) != mine.get(k):
             solver_error("config", f"the checkpoint {path} was written with {k} = {header.get(k)!r}, this run has "

@@ -191,6 +191,12 @@ class TileGroup(NativeGroup):
         periodic = resolve_periodic(options.get("test", "Sod"), options.get("periodic"))     # (refused before anything is created)
         if options.get("scalars") or getattr(options.get("test"), "scalars", None):
             _lib.solver_error("config", "passive scalars are not supported for a tile group (DESIGN.md §4.14): one block only")
+        test = options.get("test")
+        own = lambda key: options.get(key) if options.get(key) is not None else getattr(test, key, 0)
+        if own("viscosity") != 0 or own("heat_diffusivity") != 0:      # (a diffusing scalar is a scalar: refused above)
+            _lib.solver_error("config", "physical diffusion is not supported for a tile group (DESIGN.md §4.15): its stencil needs "
+                                        "a corner-carrying halo of the post-sweep state, which the exchange does not have; one "
+                                        "block only")
         L = _lib.lib()
         self.P = (int(P[0]), int(P[1]))
         nt = self.P[0] * self.P[1]

@@ -101,7 +101,8 @@ class ArmonParameters:
 
     # ref src/parameters.jl:632-670
     def _init_test(self, test="Sod", domain_size=None, origin=None, cfl=0., maxtime=0.,
-                   maxcycle=500_000, gravity=None, scalars=None, **options):
+                   maxcycle=500_000, gravity=None, scalars=None, viscosity=None, heat_diffusivity=None, diffusion_number=0.5,
+                   diffusion_max_substeps=64, **options):
         """``test``: the name of a built-in case, or a ``problem.Problem`` — a user-defined initial state, gamma, EOS and
         boundary types — which is bound here to the run's data type and cell size (``Problem.bind``).
         ``gravity=(gx, gy)``: a uniform body force, applied on the device as a kick at the end of every cycle (DESIGN.md
@@ -109,7 +110,14 @@ class ArmonParameters:
         values are rounded to the data type; ``params.test.gravity`` holds what the device receives.
         ``scalars``: a list of ``problem.Scalar`` (or a dict name → ``(NY, NX)`` array) — passive fields carried through the
         fused sweeps, added after a problem's own; at most 4 in all. ``params.scalars`` holds them bound
-        to the data type, ``params.scalar_names`` their names in plane order."""
+        to the data type, ``params.scalar_names`` their names in plane order.
+        ``viscosity=nu``, ``heat_diffusivity=chi``: physical diffusion (the rule in include/armon_hip.h) — a
+        constant kinematic shear viscosity and a constant diffusivity of the specific internal energy, both >= 0, applied on
+        the device after the cycle's last sweep and before the kick of a body force; they override a problem's own, as
+        ``gravity`` does, and a scalar diffuses with its own ``Scalar(..., diffusivity=D)``. ``params.diffusive`` says whether
+        anything diffuses. A cycle of step dt applies ``solver.diffusion_substeps(params, dt)`` equal explicit steps:
+        ``diffusion_number`` = sigma in (0, 1] bounds dt·2·kappa·(1/dx² + 1/dy²) of one of them (kappa the largest of 4 nu / 3,
+        chi and the D), and more than ``diffusion_max_substeps`` of them in a cycle is an error of the category ``time``."""
         from .problem import Problem, bind_case
         problem = test if isinstance(test, Problem) else None
         name = str(test)
@@ -122,14 +130,26 @@ class ArmonParameters:
         T = self.T
         dX = (T(self.domain_size[0]) / T(self.N[0]), T(self.domain_size[1]) / T(self.N[1]))
         if problem is not None:
-            self.test = problem.bind(dX, T, self.N, gravity=gravity, scalars=scalars)
+            self.test = problem.bind(dX, T, self.N, gravity=gravity, scalars=scalars, viscosity=viscosity,
+                                     heat_diffusivity=heat_diffusivity)
         else:
             self.test = bind_case(name, dX, T, gravity=(0., 0.) if gravity is None else gravity, scalars=scalars,
-                                  global_grid=self.N)
+                                  global_grid=self.N, viscosity=viscosity, heat_diffusivity=heat_diffusivity)
         self.scalars = tuple(self.test.scalars)
         self.scalar_names = tuple(sc.name for sc in self.scalars)
         self.gravity = self.test.gravity
         self.forced = self.gravity != (0., 0.)
+        self.viscosity, self.heat_diffusivity = self.test.viscosity, self.test.heat_diffusivity
+        self.scalar_diffusivities = tuple(sc.diffusivity for sc in self.scalars)
+        self.diffusive = self.viscosity != 0 or self.heat_diffusivity != 0 or any(D != 0 for D in self.scalar_diffusivities)
+        if isinstance(diffusion_number, (bool, np.bool_)) or not isinstance(diffusion_number, (numbers.Real, np.floating)) \
+                or not 0 < diffusion_number <= 1:
+            solver_error("config", f"diffusion_number must be a number in (0, 1], got {diffusion_number!r}")
+        self.diffusion_number = float(diffusion_number)
+        if isinstance(diffusion_max_substeps, (bool, np.bool_)) or not isinstance(diffusion_max_substeps, (numbers.Integral, np.integer)) \
+                or diffusion_max_substeps < 1:
+            solver_error("config", f"diffusion_max_substeps must be an integer >= 1, got {diffusion_max_substeps!r}")
+        self.diffusion_max_substeps = int(diffusion_max_substeps)
         self.maxcycle = int(maxcycle)
         self.cfl = float(cfl) if cfl != 0 else self.test.cfl
         self.maxtime = float(maxtime) if maxtime != 0 else self.test.maxtime
@@ -521,6 +541,12 @@ class ArmonParameters:
                                    "which compare / is_ref select too) cannot be combined with scalars")
         if self.scalars and self.use_MPI:
             solver_error("config", "passive scalars are not supported for ranks of a process group (use_MPI=true): one block only")
+        if self.diffusive and not self.use_fused_sweep:
+            solver_error("config", "physical diffusion (viscosity, heat_diffusivity, a scalar's diffusivity) runs behind the fused "
+                                   "sweeps only: use_fused_sweep=False (the staged path, which compare / is_ref select too) cannot "
+                                   "be combined with it")
+        if self.diffusive and self.use_MPI:
+            solver_error("config", "physical diffusion is not supported for ranks of a process group (use_MPI=true): one block only")
         self.exact_arithmetic = bool(exact_arithmetic)
         self.placement_tries = int(placement_tries)
         self.placement_min_bytes = int(placement_min_bytes)     # vectors smaller than this are not worth placing

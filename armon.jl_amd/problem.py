@@ -75,15 +75,39 @@ def bind_gravity(gravity, T):
     return tuple(out)
 
 
+def bind_coefficient(value, T, what):
+    """A diffusion coefficient as the device receives it: a finite number >= 0 rounded to the data type ``T``
+    → a Python float. Anything else is a configuration error that names ``what``."""
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (numbers.Real, np.floating, np.integer)) \
+            or not math.isfinite(value) or value < 0:
+        solver_error("config", f"{what} takes a finite number >= 0, got {value!r}")
+    with np.errstate(over="ignore"):
+        r = float(T(value))
+    if not math.isfinite(r):
+        solver_error("config", f"{what} = {value!r} is not finite in {np.dtype(T).name}")
+    return r if r != 0 else 0.
+
+
+def diffusion_description(nu, chi, scalars):
+    """What a checkpoint's header and a problem's digest say about a diffusive run: ``{"nu", "chi", "scalars": {name: D}}`` with
+    the floats as hex text — or None when nothing diffuses, and the headers and digests of such runs stay what they were."""
+    D = {sc.name: float(sc.diffusivity).hex() for sc in scalars if sc.diffusivity != 0}
+    if nu == 0 and chi == 0 and not D:
+        return None
+    return {"nu": float(nu).hex(), "chi": float(chi).hex(), "scalars": D}
+
+
 @dataclasses.dataclass(frozen=True)
 class BoundTestCase(TestCase):
     """A built-in case bound to a run: the ``TestCase`` of ``create_test`` with the run's body force, rounded to its data type."""
     gravity: tuple = (0., 0.)
     scalars: tuple = ()          # the run's passive scalars (BoundScalar), sampled with samples = 1
     samples: int = 1
+    viscosity: float = 0.        # the run's diffusion coefficients (DESIGN.md §4.15), rounded to its data type
+    heat_diffusivity: float = 0.
 
 
-def bind_case(name, dX, T, gravity=(0., 0.), scalars=None, global_grid=None):
+def bind_case(name, dX, T, gravity=(0., 0.), scalars=None, global_grid=None, viscosity=None, heat_diffusivity=None):
     """``create_test(name, dX, T)`` with the body force ``gravity`` of the run (``bind_gravity``) and its passive ``scalars``
     → ``BoundTestCase``; a forced case is not ``conservative``."""
     case = create_test(name, dX, T)
@@ -91,7 +115,10 @@ def bind_case(name, dX, T, gravity=(0., 0.), scalars=None, global_grid=None):
     kw = {f.name: getattr(case, f.name) for f in dataclasses.fields(case)}
     if gravity != (0., 0.):
         kw["conservative"] = False
-    return BoundTestCase(gravity=gravity, scalars=bind_scalars(scalars, T, global_grid), **kw)
+    return BoundTestCase(gravity=gravity, scalars=bind_scalars(scalars, T, global_grid),
+                         viscosity=bind_coefficient(0. if viscosity is None else viscosity, T, "viscosity"),
+                         heat_diffusivity=bind_coefficient(0. if heat_diffusivity is None else heat_diffusivity, T, "heat_diffusivity"),
+                         **kw)
 
 
 class State:
@@ -191,14 +218,16 @@ class Scalar:
     include/armon_hip.h). ``background``: φ of every point no region holds; ``regions``: a list of ``(shape, value)`` with the
     shapes of a ``Problem``, of which the LAST one that holds a point gives φ; a cut cell takes the volume mean of its sample
     points (the problem's ``samples``). ``array``: φ as a global ``(NY, NX)`` array of the real cells instead. Values are any
-    finite numbers; nothing bounds φ afterwards either (a second-order remap overshoots)."""
+    finite numbers; nothing bounds φ afterwards either (a second-order remap overshoots). ``diffusivity``: the constant D >= 0
+    with which φ diffuses; 0 = a purely advected field."""
 
-    def __init__(self, name, background=0., regions=(), array=None):
+    def __init__(self, name, background=0., regions=(), array=None, diffusivity=0.):
         if not isinstance(name, str) or name == "":
             solver_error("config", f"the name of a scalar is a non-empty string, got {name!r}")
         if ":" in name:
             solver_error("config", f"the name of a scalar must not contain ':', got {name!r}")
         self.name = name
+        self.diffusivity = bind_coefficient(diffusivity, np.float64, f"the diffusivity of the scalar {name!r}")
         self.background = _finite(background, f"the background of the scalar {name!r}")
         self.regions = list(regions)
         if len(self.regions) > MAX_REGIONS:
@@ -255,6 +284,7 @@ class BoundScalar:
 
     def __init__(self, scalar, T, global_grid=None):
         self.name, self.T = scalar.name, T
+        self.diffusivity = bind_coefficient(scalar.diffusivity, T, f"the diffusivity of the scalar {scalar.name!r}")
         hx = lambda vals: [float(v).hex() for v in vals]
         with np.errstate(over="ignore"):
             if scalar.array is not None:
@@ -319,13 +349,17 @@ class Problem:
     not come back in on the other (build such a state with several shapes, or ``from_arrays``).
     ``gravity = (gx, gy)``: a uniform body force, applied as a kick at the end of every cycle; a forced
     problem is not held to energy conservation. ``scalars``: a list of ``Scalar`` — passive fields carried by the flow
-    (DESIGN.md §4.14); ``from_arrays`` also takes a dict name → ``(NY, NX)`` array. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
+    (DESIGN.md §4.14); ``from_arrays`` also takes a dict name → ``(NY, NX)`` array. ``viscosity``, ``heat_diffusivity``: the
+    constant kinematic shear viscosity and the diffusivity of the specific internal energy, both >= 0; the
+    options of the same names of ``ArmonParameters`` override them. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
     the options of ``ArmonParameters`` override."""
 
     def __init__(self, name, background, regions=(), gamma=7 / 5, eos="perfect_gas", boundaries=Dirichlet, domain_size=(1., 1.),
                  origin=(0., 0.), cfl=0.5, maxtime=0.2, conservative=True, samples=1, gravity=(0., 0.), scalars=(), _deferred=None,
-                 _arrays=None):
+                 _arrays=None, viscosity=0., heat_diffusivity=0.):
         self.name = str(name)
+        self.viscosity = bind_coefficient(viscosity, np.float64, "viscosity")
+        self.heat_diffusivity = bind_coefficient(heat_diffusivity, np.float64, "heat_diffusivity")
         self.scalars = check_scalars(scalars)
         self.gravity = bind_gravity(gravity, np.float64)
         self.gamma = _finite(gamma, "gamma")
@@ -441,17 +475,19 @@ class Problem:
         return cls(name, None, (), _arrays=arrays, **options)
 
     # ---- binding ---------------------------------------------------------------------------------------------------------
-    def bind(self, dX, T=np.float64, global_grid=None, gravity=None, scalars=None):
+    def bind(self, dX, T=np.float64, global_grid=None, gravity=None, scalars=None, viscosity=None, heat_diffusivity=None):
         """This problem for a run in the data type ``T`` with cells ``dX`` on ``global_grid = (NX, NY)`` → ``BoundProblem``.
         ``gravity``: the run's own body force instead of the problem's (the ``gravity`` option of ``ArmonParameters``).
         ``scalars``: the run's own passive scalars, after the problem's (the ``scalars`` option)."""
         T = np.dtype(T).type
         gravity = bind_gravity(self.gravity if gravity is None else gravity, T)
         extra = check_scalars(scalars)
+        nu = bind_coefficient(self.viscosity if viscosity is None else viscosity, T, "viscosity")
+        chi = bind_coefficient(self.heat_diffusivity if heat_diffusivity is None else heat_diffusivity, T, "heat_diffusivity")
         key = (T, float(dX[0]), float(dX[1]), None if global_grid is None else tuple(global_grid), gravity,
-               tuple(id(sc) for sc in extra))
+               tuple(id(sc) for sc in extra), nu, chi)
         if key not in self._cache:
-            self._cache = {key: BoundProblem(self, dX, T, global_grid, gravity, check_scalars(self.scalars + extra))}
+            self._cache = {key: BoundProblem(self, dX, T, global_grid, gravity, check_scalars(self.scalars + extra), nu, chi)}
             self._cache_scalars = extra        # (keeps the ids of the key alive)
         return self._cache[key]
 
@@ -466,9 +502,11 @@ class BoundProblem:
     tag = INIT_TAG
     r = 0.
 
-    def __init__(self, problem, dX, T, global_grid, gravity=(0., 0.), scalars=()):
+    def __init__(self, problem, dX, T, global_grid, gravity=(0., 0.), scalars=(), viscosity=0., heat_diffusivity=0.):
         P = self.problem = problem
         self.scalars = bind_scalars(scalars, T, global_grid)
+        self.viscosity = bind_coefficient(viscosity, T, "viscosity")          # the values the device receives
+        self.heat_diffusivity = bind_coefficient(heat_diffusivity, T, "heat_diffusivity")
         self.gravity = bind_gravity(gravity, T)            # the two values the device receives
         self.name, self.header_name = P.name, "Problem:" + P.name
         self.gamma, self.eos, self.boundaries, self.samples = P.gamma, P.eos, P.boundaries, P.samples
@@ -497,6 +535,9 @@ class BoundProblem:
             self.description["gravity"] = hx(self.gravity)
         if self.scalars:                            # only then, likewise
             self.description["scalars"] = [sc.description for sc in self.scalars]
+        diffusion = diffusion_description(self.viscosity, self.heat_diffusivity, self.scalars)
+        if diffusion is not None:                   # only then, likewise
+            self.description["diffusion"] = diffusion
         self.digest = hashlib.sha256(json.dumps(self.description, sort_keys=True).encode("utf-8")).hexdigest()
 
     def _bind_arrays(self, src, global_grid):

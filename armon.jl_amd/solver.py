@@ -42,6 +42,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     history: object = None                               # history.History of history_step
     images: list = field(default_factory=list)          # paths of the frames of image_step / image_at_end
     scalars: tuple = ()                                  # names of the run's passive scalars (read with stats.data.scalar(name))
+    diffusion_steps: int = 0                             # launches of armon_hip_diffuse: the sub-steps of every cycle
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -189,6 +190,7 @@ class BlockGrid:
             self.alt[f] = dev.zeros(n, dt_)
         self.placement = None                  # report of tune_placement (bench / tests)
         self.pair_cycles = 0                   # host-driven cycles that went through armon_hip_sweep_pair (a report, like placement)
+        self.diffusion_steps = 0               # launches of armon_hip_diffuse (a report, likewise)
         self.global_dt = GlobalTimeStep(params)
         self.dt_scalar = dev.zeros(2, dt_)     # device scalar written by the fused dt reduction
         self.dt = DtReadback(params)           # deferred read-back of dt_scalar
@@ -747,6 +749,74 @@ def body_force(params, grid, dt):
                                       p("v") if gy != 0 else None, p("E")))
 
 
+def diffusion_substeps(params, dt):
+    """How many equal explicit steps a cycle of step ``dt`` applies its physical diffusion in:
+    ``n = max(1, ceil(float(dt)·2·κ·(1/dx² + 1/dy²)/σ))`` with κ the largest of 4·nu/3, chi and the scalars' D, and σ =
+    ``diffusion_number``; each step has the length ``T(dt)/T(n)``. More than ``diffusion_max_substeps`` is an error of the
+    category ``time`` that names the three numbers. 0 when nothing diffuses."""
+    if not params.diffusive:
+        return 0
+    dx, dy = float(params.cell_size(0)), float(params.cell_size(1))
+    kappa = max(4. * params.viscosity / 3., params.heat_diffusivity, *params.scalar_diffusivities)
+    number = float(dt) * 2. * kappa * (1. / (dx * dx) + 1. / (dy * dy))
+    n = max(1, math.ceil(number / params.diffusion_number))
+    if n > params.diffusion_max_substeps:
+        solver_error("time", f"a cycle of step dt = {float(dt)!r} has the diffusion number {number!r}: it needs {n} sub-steps at "
+                             f"diffusion_number = {params.diffusion_number!r}, more than diffusion_max_substeps = "
+                             f"{params.diffusion_max_substeps}")
+    return n
+
+
+def diffuse_desc(params, grid, dt):
+    """The ``armon_diffuse_desc`` of one step of length ``dt`` of ``grid``'s current state and its diffusing planes into their
+    ping-pong partners. A state that does not diffuse (nu = chi = 0) is left where it is: its arrays are not given."""
+    d = _lib.DiffuseDesc()
+    d.nx, d.ny = params.N
+    d.nghost = params.nghost
+    for k, side in enumerate((Side.Left, Side.Right, Side.Bottom, Side.Top)):          # the ARMON_SIDE_* order
+        d.periodic[k] = int(params.wrap[k // 2])
+        d.u_factor[k], d.v_factor[k] = params.test.boundary_condition(side)
+    d.dt, d.dx, d.dy = float(dt), params.cell_size(0), params.cell_size(1)
+    d.nu, d.chi = params.viscosity, params.heat_diffusivity
+    d.rho = grid.data["rho"].ptr
+    if params.viscosity != 0 or params.heat_diffusivity != 0:
+        d.u, d.v, d.E = (grid.data[f].ptr for f in ("u", "v", "E"))
+        d.rho_out, d.u_out, d.v_out, d.E_out = (grid.alt[f].ptr for f in STATE_VARS)
+    planes = diffusing_planes(params, grid)
+    d.ns = len(planes)
+    for k, (f, D) in enumerate(planes):
+        d.D[k], d.phi[k], d.phi_out[k] = D, grid.data[f].ptr, grid.alt[f].ptr
+    return d
+
+
+def diffusing_planes(params, grid):
+    """``(plane, D)`` of the scalars with a diffusivity, in plane order."""
+    return [(f, D) for f, D in zip(grid.scalar_planes, params.scalar_diffusivities) if D != 0]
+
+
+def diffuse(params, grid, dt):
+    """The physical diffusion of a cycle of step ``dt`` (``params.viscosity``, ``heat_diffusivity``, the scalars' own;
+    DESIGN.md §4.15, the rule in include/armon_hip.h): ``diffusion_substeps`` launches of ``armon_hip_diffuse`` on the compute
+    stream, each followed by the swap of what it wrote with its ping-pong partner — the whole set of four state vectors (the
+    step copies ρ, so that the two placement-tuned sets stay together) and the diffusing planes. After the cycle's last sweep,
+    before the kick of a body force. Without diffusion nothing is launched."""
+    if not params.diffusive:
+        return
+    n = diffusion_substeps(params, dt)
+    T = params.T
+    step = float(T(dt) / T(n))
+    state = params.viscosity != 0 or params.heat_diffusivity != 0
+    for _ in range(n):
+        d = diffuse_desc(params, grid, step)
+        with _k(params, "diffuse"):
+            check(params.fn("diffuse")(params.device.ctx, C.byref(d)))
+        grid.diffusion_steps += 1
+        if state:
+            grid.swap_state()
+        for f, _D in diffusing_planes(params, grid):
+            grid.data[f], grid.alt[f] = grid.alt[f], grid.data[f]
+
+
 def local_time_step(params, grid):
     """ref src/reductions.jl:89-110 (dx, dy are the GLOBAL cell sizes, :92)"""
     r = _range(params, params.steps_ranges[Axis.X].real_domain)
@@ -1086,7 +1156,8 @@ def solver_cycle(params, grid, last_cycle=True):
         fused_pair(params, grid, d_x, d_y)
         grid.pair_cycles += 1
         if not params.cst_dt:
-            post_dt_readback(params, grid)       # (the Y sweep's own CFL step: that of the velocities before the kick)
+            post_dt_readback(params, grid)       # (the Y sweep's own CFL step: that of the velocities before diffusion and kick)
+        diffuse(params, grid, dt)
         body_force(params, grid, dt)
         if not params.cst_dt:
             if deferred:
@@ -1105,8 +1176,10 @@ def solver_cycle(params, grid, last_cycle=True):
             sweep = rank_sweep if params.use_MPI else fused_sweep
             sweep(params, grid, axis, dt, dx, emit_p=last and last_cycle, emit_dt=last and not params.cst_dt)
             if last:
-                # the kick of a body force: after the cycle's last sweep (whose strips, if any, the compute stream has
-                # joined), before the halo of the next cycle is packed from the real cells it changes
+                # physical diffusion, then the kick of a body force: after the cycle's last sweep (whose strips, if any, the
+                # compute stream has joined), before the halo of the next cycle is packed from the real cells they change.
+                # The sweep's emitted CFL step is that of the velocities before either.
+                diffuse(params, grid, gdt.current_dt)
                 body_force(params, grid, gdt.current_dt)
             if last and not last_cycle:
                 prefetch_halo(params, grid)
@@ -1159,6 +1232,8 @@ def graph_cycles_usable(params):
         return False                    # and an image frame rendered
     if params.forced:
         return False                    # and the kick of a body force enqueued behind every cycle (not part of the captured graph)
+    if params.diffusive:
+        return False                    # and the diffusion steps enqueued behind every cycle (host-driven only)
     if params.scalar_names:
         return False                    # and the scalar sweep enqueued behind every sweep (host-driven only)
     if params.use_MPI or any(n != PROC_NULL for n in params.neighbours.values()):
@@ -1499,6 +1574,7 @@ def armon(params):
     stats.history = grid.history
     stats.images = list(grid.images)
     stats.scalars = tuple(params.scalar_names)
+    stats.diffusion_steps = grid.diffusion_steps
     if params.return_data:
         stats.data = grid
     return stats

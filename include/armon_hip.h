@@ -983,6 +983,101 @@ ARMON_API int armon_hip_sweep_scalars(armon_ctx*, const armon_sweep_desc*, int n
 ARMON_API int armon_hip_sweep_scalars_f32(armon_ctx*, const armon_sweep_desc_f32*, int ns, const float* const* phi_in,
                                           float* const* phi_out);
 
+/* ---- physical diffusion: viscosity, heat conduction and scalar diffusivity (csrc/diffuse.hip) -------- */
+/* No reference counterpart: the reference solves the inviscid equations. Operator-split, one or more steps per cycle. The rule:
+ *
+ * Coefficients. All are constants, >= 0 and finite:
+ * - nu: kinematic shear viscosity. The bulk viscosity is 0.
+ * - chi: diffusivity of the specific internal energy e = E − ½(u² + v²). For the perfect gas this is Fourier conduction with
+ *   k = ρ·chi·c_v. It is defined the same way for Bizarrium. No EOS is evaluated.
+ * - D_k: one per diffusing scalar plane.
+ *
+ * Shape of the step. One step of length dt reads ρ, u, v, E and the diffusing planes φ_k. It writes u', v', E', φ_k' of the REAL
+ * cells into other arrays. It is out of place. ρ does not change. It reads no ghost cell. It writes no ghost cell or padding.
+ *
+ * Arithmetic.
+ * - T is the run's data type.
+ * - One IEEE operation per operation written. No contraction. The only division is dt / ρ.
+ * - The host passes idx = T(1)/dx and idy = T(1)/dy.
+ * - The kernel forms q4x = T(0.25)·idx, q4y = T(0.25)·idy, c43 = T(4)/T(3) and c23 = T(2)/T(3).
+ *
+ * Cells outside the domain. A neighbour index outside [0, n) along an axis maps as follows:
+ * - On a Periodic axis: the wrapped index.
+ * - Otherwise: the mirrored one, −1−i or 2n−1−i, with u and v multiplied by that side's u_factor and v_factor. These are the
+ *   sweep's own factors, ±1. ρ, e and φ take factor +1.
+ * - Both axes map independently. Factors multiply in a corner.
+ * A wall is therefore free-slip, adiabatic and impermeable to φ. Its face carries zero tangential stress, zero work and zero heat
+ * and scalar flux.
+ *
+ * Flux of the x-face. Take the face between cells L = (i, j) and R = (i+1, j):
+ * - rf = T(0.5)·(ρ_L + ρ_R)
+ * - mu = nu·rf
+ * - ux = (u_R − u_L)·idx
+ * - vx = (v_R − v_L)·idx
+ * - uy = ((u[i,j+1] − u[i,j−1]) + (u[i+1,j+1] − u[i+1,j−1]))·q4y
+ * - vy likewise from v
+ * - txx = mu·(c43·ux − c23·vy)
+ * - txy = mu·(uy + vx)
+ * - uf = T(0.5)·(u_L + u_R)
+ * - vf likewise
+ * - q = (chi·rf)·((e_R − e_L)·idx)
+ * - F_u = txx
+ * - F_v = txy
+ * - F_E = (uf·txx + vf·txy) + q
+ * - F_φk = (D_k·rf)·((φ_R − φ_L)·idx)
+ *
+ * Flux of the y-face. This is the transpose:
+ * - normal differences with idy;
+ * - the transverse ones ((a[i+1,j] − a[i−1,j]) + (a[i+1,j+1] − a[i−1,j+1]))·q4x;
+ * - tyy = mu·(c43·vy − c23·ux);
+ * - G_u = txy, G_v = tyy, G_E = (uf·txy + vf·tyy) + q.
+ *
+ * Update. With k = dt/ρ:
+ *   a' = a + k·((F_a(i+½) − F_a(i−½))·idx + (G_a(j+½) − G_a(j−½))·idy)
+ * for a = u, v, E, φ_k.
+ *
+ * Consequences to preserve.
+ * - A face's flux is ONE value whichever of its two cells evaluates it: "right minus left", with commutative sums only.
+ * - So Σρu, Σρv, ΣρE and Σρφ telescope.
+ * - A uniform state is a fixed point bit for bit.
+ *
+ * armon_hip_diffuse: ONE launch on the context's stream for the state and the `ns` diffusing planes, in the layout of the state
+ * vectors (flat, ghosted, plain pitch nx + 2·nghost). periodic / u_factor / v_factor are indexed by ARMON_SIDE_*; the factors of
+ * a periodic side are not used. With nu = chi = 0 the planes alone are read and written (ρ is read; u, v, E and their outputs
+ * are not looked at and may be NULL); with ns = 0 the state alone. With rho_out given the real cells of ρ are copied too, so
+ * that the caller swaps the whole set of four: 64 B per fp64 cell for the state, 16 B more per plane. All of nu, chi and
+ * D[0..ns) zero: ARMON_OK, nothing launched, no pointer looked at. Refused before any launch (ARMON_ERR_INVALID_ARG, nothing
+ * written; armon_hip_last_error names the argument): a NULL ctx or descriptor; a NULL array that the step reads or writes; an
+ * output that is an input or another output (the same pointer: arrays that overlap in part are not detected and are the
+ * caller's to avoid); a negative or non-finite nu, chi, D[k] or dt; dx or dy not finite and positive;
+ * a factor of a non-periodic side other than +1 / -1; ns outside 0..ARMON_MAX_SCALARS; nx or ny < 1, nghost < 0, or a block
+ * whose runs of rows outgrow a launch grid; a periodic flag on one side of an axis only. */
+typedef struct armon_diffuse_desc {
+    int64_t nx, ny;
+    int32_t nghost, ns;
+    int32_t periodic[4];
+    double  u_factor[4], v_factor[4];
+    double  dt, dx, dy, nu, chi, D[ARMON_MAX_SCALARS];
+    const double *rho, *u, *v, *E;
+    double *rho_out, *u_out, *v_out, *E_out;
+    const double* phi[ARMON_MAX_SCALARS];
+    double* phi_out[ARMON_MAX_SCALARS];
+} armon_diffuse_desc;
+/* fp32: field for field the same, with float arrays; the scalars stay double and are rounded to float inside. */
+typedef struct armon_diffuse_desc_f32 {
+    int64_t nx, ny;
+    int32_t nghost, ns;
+    int32_t periodic[4];
+    double  u_factor[4], v_factor[4];
+    double  dt, dx, dy, nu, chi, D[ARMON_MAX_SCALARS];
+    const float *rho, *u, *v, *E;
+    float *rho_out, *u_out, *v_out, *E_out;
+    const float* phi[ARMON_MAX_SCALARS];
+    float* phi_out[ARMON_MAX_SCALARS];
+} armon_diffuse_desc_f32;
+ARMON_API int armon_hip_diffuse(armon_ctx*, const armon_diffuse_desc*);
+ARMON_API int armon_hip_diffuse_f32(armon_ctx*, const armon_diffuse_desc_f32*);
+
 
 /* ---- multi-GPU: tile-decomposed grid, halo exchange and dt reduction on the device ------------------------------ */
 /* Replaces the reference's MPI path: start_exchange / finish_exchange (ref src/halo_exchange.jl:229-283), the side
