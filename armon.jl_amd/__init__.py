@@ -7,6 +7,7 @@ Public surface = the reference's exports (ref src/Armon.jl:15-16): ``ArmonParame
 """
 from ._lib import LIB_PATH, SolverException, lib          # noqa: F401
 from .blocking import Axis, BlockSize, DomainRange, Side, StepRange   # noqa: F401
+from .mixing import MixingProfile, ScalarPDF, mixing_state, pdf_state   # noqa: F401
 from .parameters import ArmonParameters, memory_required   # noqa: F401
 from .problem import Box, Disc, Ellipse, HalfPlane, Problem, Scalar, State   # noqa: F401
 from .solver import BlockGrid, SolverStats, armon          # noqa: F401

@@ -145,6 +145,23 @@ class DiffuseDesc(C.Structure):
                 ("phi", C.c_void_p * 4), ("phi_out", C.c_void_p * 4)]
 
 
+class MixingBin(C.Structure):
+    """armon_mixing_bin — one (plane, bin) of the mixing measures, 20 words (include/armon_hip.h, armon_hip_mixing)."""
+    _fields_ = [("n", C.c_uint64), ("n_bad", C.c_uint64), ("sum", (C.c_int64 * 3) * 5),
+                ("phi_min", C.c_uint64), ("phi_max", C.c_uint64), ("reserved", C.c_uint64)]
+
+
+class MixingSpec(C.Structure):
+    """armon_mixing_spec — the axis and the bins of the mixing measures, and the quanta of every plane's sums."""
+    _fields_ = [("axis", C.c_int32), ("reserved", C.c_int32), ("nbins", C.c_int64), ("width", C.c_int64),
+                ("scale_exp", (C.c_int32 * 5) * 4)]
+
+
+class PdfSpec(C.Structure):
+    """armon_pdf_spec — the bins of a scalar's histogram and the quantum of its mass sums."""
+    _fields_ = [("lo", C.c_double), ("inv_w", C.c_double), ("nbins", C.c_int32), ("rho_scale_exp", C.c_int32)]
+
+
 class HaloDesc(C.Structure):
     """armon_halo_desc — what one local tile exchanges (include/armon_hip.h)."""
     _fields_ = [("nx", C.c_int64), ("ny", C.c_int64), ("nghost", C.c_int32), ("nvars", C.c_int32),
@@ -262,6 +279,12 @@ SIGNATURES = {
                                          C.c_size_t, _ci, _dbl, C.POINTER(_ci * 8), C.POINTER(_dbl), C.POINTER(_ci)]),
     "armon_hip_sweep_scalars": (_ci, [_vp, C.POINTER(SweepDesc), _ci, C.POINTER(_dp), C.POINTER(_dp)]),
     "armon_hip_diffuse": (_ci, [_vp, C.POINTER(DiffuseDesc)]),
+    "armon_hip_mixing_reset": (_ci, [_vp, _ci, _i64, _dp]),
+    "armon_hip_mixing": (_ci, [_vp, _i64, _ci, _i64, _i64, _dp, _ci, C.POINTER(_dp)] + [_i64] * 6 + [C.POINTER(MixingSpec), _dp]),
+    "armon_hip_mixing_bounds": (_ci, [_vp, _i64, _ci, _i64, _i64, _dp, _ci, C.POINTER(_dp)] + [_i64] * 6
+                                + [C.POINTER(MixingSpec), _dp]),
+    "armon_hip_scalar_pdf_reset": (_ci, [_vp, _ci, _dp]),
+    "armon_hip_scalar_pdf": (_ci, [_vp, _i64, _ci, _i64, _i64, _dp, _dp] + [_i64] * 4 + [C.POINTER(PdfSpec), _dp]),
     "armon_hip_mgpu_init": (_ci, [_ci, _ci, C.POINTER(_ci), C.POINTER(_vp)]),
     "armon_hip_mgpu_unique_id": (_ci, [_vp]),
     "armon_hip_mgpu_init_rank": (_ci, [_ci, _ci, _ci, _ci, _vp, _vp, C.POINTER(_vp)]),
@@ -322,6 +345,9 @@ def _add_f32_signatures():
     SIGNATURES["armon_hip_periodic_ghosts_f32"] = SIGNATURES["armon_hip_periodic_ghosts"]
     SIGNATURES["armon_hip_profile_f32"] = SIGNATURES["armon_hip_profile"]
     SIGNATURES["armon_hip_profile_bounds_f32"] = SIGNATURES["armon_hip_profile_bounds"]
+    SIGNATURES["armon_hip_mixing_f32"] = SIGNATURES["armon_hip_mixing"]
+    SIGNATURES["armon_hip_mixing_bounds_f32"] = SIGNATURES["armon_hip_mixing_bounds"]
+    SIGNATURES["armon_hip_scalar_pdf_f32"] = SIGNATURES["armon_hip_scalar_pdf"]
     SIGNATURES["armon_hip_exact_norms_f32"] = SIGNATURES["armon_hip_exact_norms"]
     SIGNATURES["armon_hip_exact_fill_f32"] = SIGNATURES["armon_hip_exact_fill"]
     SIGNATURES["armon_hip_history_sample_f32"] = SIGNATURES["armon_hip_history_sample"]

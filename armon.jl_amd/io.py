@@ -300,6 +300,96 @@ def read_profile_file(path):
     return t
 
 
+MIXING_COLUMNS = ("coord", "n", "rho", "phi", "phi_favre", "variance", "favre_variance", "phi_min", "phi_max")
+MIXING_MEASURES = ("content", "min", "max", "width", "mixedness", "extent_lo", "extent_hi")
+
+
+def write_mixing_file(path, profiles, pdfs=None, precision=17):
+    """One mixing sample (dict name → mixing.MixingProfile, dict name → mixing.ScalarPDF or None) as text: a header line —
+    cycle, time, how many scalars and histograms — then per scalar a block of profile columns (a line naming the scalar, the
+    axis, the width and the bins; a line naming the columns; one line per bin), and below them per histogram a block of
+    ``edge_lo, edge_hi, count, mass`` (a line naming the scalar, the range, the bins, the bad count and what fell below and
+    above; one line per bin), at ``precision`` digits (17 reads back bit for bit)."""
+    fmt = _fmt(precision)
+    tables = [p.table() for p in profiles.values()]
+    with open(path, "w") as f:
+        f.write(f"# mixing cycle={tables[0]['cycle']} time={(fmt % tables[0]['time']).strip()} scalars={len(tables)} "
+                f"pdfs={len(pdfs or {})}\n")
+        for t in tables:
+            f.write(f"# scalar name={t['name']} axis={t['axis']} width={t['width']} nbins={len(t['n'])}\n")
+            f.write("# " + ", ".join(MIXING_COLUMNS) + "\n")
+            for b in range(len(t["n"])):
+                f.write(", ".join(str(int(t[c][b])) if c == "n" else fmt % t[c][b] for c in MIXING_COLUMNS) + "\n")
+        for pdf in (pdfs or {}).values():
+            t = pdf.table()
+            f.write(f"# pdf name={t['name']} lo={(fmt % t['lo']).strip()} hi={(fmt % t['hi']).strip()} nbins={t['nbins']} bad={t['bad']} "
+                    f"below_n={t['below'][0]} below_mass={(fmt % t['below'][1]).strip()} above_n={t['above'][0]} "
+                    f"above_mass={(fmt % t['above'][1]).strip()}\n")
+            f.write("# edge_lo, edge_hi, count, mass\n")
+            for b in range(t["nbins"]):
+                f.write(f"{fmt % t['edges'][b]}, {fmt % t['edges'][b + 1]}, {int(t['counts'][b])}, {fmt % t['mass'][b]}\n")
+
+
+def read_mixing_file(path):
+    """→ ``(profiles, pdfs)``: dict name → the dict of ``MixingProfile.table()``, and dict name → the dict of
+    ``ScalarPDF.table()`` or None when the file holds no histogram."""
+    with open(path) as f:
+        lines = [line.rstrip("\n") for line in f if line.strip()]
+    head = dict(item.split("=", 1) for item in lines[0].split()[2:])
+    cycle, time = int(head["cycle"]), float(head["time"])
+    profiles, pdfs, at = {}, {}, 1
+    for _ in range(int(head["scalars"])):
+        h = dict(item.split("=", 1) for item in lines[at].split()[2:])
+        nb = int(h["nbins"])
+        rows = [[v.strip() for v in line.split(",")] for line in lines[at + 2:at + 2 + nb]]
+        t = {"name": h["name"], "axis": h["axis"], "width": int(h["width"]), "cycle": cycle, "time": time}
+        for k, c in enumerate(MIXING_COLUMNS):
+            t[c] = np.array([int(r[k]) for r in rows], dtype=np.uint64) if c == "n" else np.array([float(r[k]) for r in rows], dtype=np.float64)
+        profiles[t["name"]] = t
+        at += 2 + nb
+    for _ in range(int(head["pdfs"])):
+        h = dict(item.split("=", 1) for item in lines[at].split()[2:])
+        nb = int(h["nbins"])
+        rows = [[v.strip() for v in line.split(",")] for line in lines[at + 2:at + 2 + nb]]
+        edges = [float(r[0]) for r in rows] + [float(rows[-1][1])]
+        pdfs[h["name"]] = {"name": h["name"], "lo": float(h["lo"]), "hi": float(h["hi"]), "nbins": nb, "bad": int(h["bad"]),
+                           "below": (int(h["below_n"]), float(h["below_mass"])), "above": (int(h["above_n"]), float(h["above_mass"])),
+                           "edges": np.array(edges, dtype=np.float64), "counts": np.array([int(r[2]) for r in rows], dtype=np.uint64),
+                           "mass": np.array([float(r[3]) for r in rows], dtype=np.float64)}
+        at += 2 + nb
+    return profiles, (pdfs or None)
+
+
+def write_mixing_series(path, samples, precision=17):
+    """The time series of a run's mixing samples ``(cycle, time, profiles, pdfs)`` as text: a header line naming the scalars,
+    a line naming the columns, then one line per sample: cycle, time, and per scalar the content, the minimum, the maximum,
+    the integral width W, the mixedness Θ and both ends of ``extent()`` (NaN where there is none)."""
+    fmt = _fmt(precision)
+    names = list(samples[0][2]) if samples else []
+    with open(path, "w") as f:
+        f.write("# mixing_series scalars=" + ",".join(names) + "\n")
+        f.write("# cycle, time" + "".join(f", {s}:{m}" for s in names for m in MIXING_MEASURES) + "\n")
+        for cycle, time, profiles, _ in samples:
+            values = [profiles[s].measures()[m] for s in names for m in MIXING_MEASURES]
+            f.write(", ".join([str(int(cycle)), fmt % time] + [fmt % v for v in values]) + "\n")
+
+
+def read_mixing_series(path):
+    """→ dict: ``scalars`` (names), ``cycle`` (int64 array), ``time`` (fp64 array) and per scalar name a dict measure → fp64
+    array, the measures being ``MIXING_MEASURES``."""
+    with open(path) as f:
+        head = f.readline().split()[2]
+        f.readline()
+        rows = [[v.strip() for v in line.split(",")] for line in f if line.strip()]
+    names = [s for s in head.split("=", 1)[1].split(",") if s]
+    t = {"scalars": names, "cycle": np.array([int(r[0]) for r in rows], dtype=np.int64),
+         "time": np.array([float(r[1]) for r in rows], dtype=np.float64)}
+    for i, s in enumerate(names):
+        t[s] = {m: np.array([float(r[2 + i * len(MIXING_MEASURES) + k]) for r in rows], dtype=np.float64)
+                for k, m in enumerate(MIXING_MEASURES)}
+    return t
+
+
 ERROR_NORMS_COLUMNS = ("l1", "l2", "linf", "bias")
 
 

@@ -270,7 +270,8 @@ class ArmonParameters:
                      start_from_exact=None, history_step=0, history_file="history", history_gauges=(), history_capacity=256,
                      history_scale_exp=None, image_step=0, image_at_end=False, image_quantity="grad_rho", image_reduce=None,
                      image_coarsen=None, image_transfer=None, image_range=None, image_file="image", checkpoint_compress=False,
-                     **options):
+                     mixing_step=0, mixing_at_end=False, mixing_axis="y", mixing_bin_width=1, mixing_scalars=None,
+                     mixing_pdf_bins=0, mixing_pdf_range=(0., 1.), mixing_file="mixing", **options):
         """``checkpoint_step=k``: a checkpoint every k completed cycles (0 = off) as
         ``<output_dir>/<checkpoint_file>_<cycle:06d>.ckpt``; ``checkpoint_at_end``: one when the run stops;
         ``restart_from=path``: continue the run of that file, bit for bit (checkpoint.py; no reference counterpart);
@@ -308,7 +309,14 @@ class ArmonParameters:
         (None: ``output_coarsen`` if set, else the smallest power of two that brings the longer side to at most 2048
         pixels); ``image_transfer``: ``"linear" | "log" | "schlieren"`` or a dict quantity → name (None: schlieren for
         ``grad_rho``, linear otherwise); ``image_range=(lo, hi)``: the values of black and white (None: the frame's own
-        finite minimum and maximum)."""
+        finite minimum and maximum).
+        ``mixing_step=k``: after every k completed cycles (0 = off) the mixing measures of the run's passive scalars
+        (mixing.py) — per scalar the exact profile of rho, φ, φ², ρφ, ρφ² along ``mixing_axis`` = ``"x" | "y"`` in bins of
+        ``mixing_bin_width`` cells, and with ``mixing_pdf_bins`` > 0 the histogram of φ over ``mixing_pdf_range = (lo, hi)``
+        with the mass of every bin — are written to ``<output_dir>/<mixing_file>_<cycle:06d>.txt``, their whole-record
+        measures (content, min, max, integral width, mixedness, extents) to one line of the time series
+        ``<output_dir>/<mixing_file>.txt``, and listed in ``SolverStats.mixing``; ``mixing_scalars``: the names to take
+        (None = all); ``mixing_at_end``: one sample when the run stops. A restart starts a new series. One block only."""
         self.compare, self.is_ref = bool(compare), bool(is_ref)
         if isinstance(checkpoint_step, bool) or not isinstance(checkpoint_step, (numbers.Integral, np.integer)) or checkpoint_step < 0:
             solver_error("config", f"checkpoint_step must be an integer >= 0, got {checkpoint_step!r}")
@@ -382,6 +390,47 @@ class ArmonParameters:
         if self.state_profile and self.use_MPI:
             solver_error("config", "profile_step / profile_at_end are not supported for ranks of a process group (use_MPI=true): "
                                    "one block or an in-process tile group only")
+        if isinstance(mixing_step, bool) or not isinstance(mixing_step, (numbers.Integral, np.integer)) or mixing_step < 0:
+            solver_error("config", f"mixing_step must be an integer >= 0, got {mixing_step!r}")
+        self.mixing_step = int(mixing_step)
+        if not isinstance(mixing_at_end, (bool, np.bool_)):
+            solver_error("config", f"mixing_at_end must be True or False, got {mixing_at_end!r}")
+        self.mixing_at_end = bool(mixing_at_end)
+        if mixing_axis not in ("x", "y"):
+            solver_error("config", f"unknown mixing_axis {mixing_axis!r}: 'x' or 'y'")
+        self.mixing_axis = str(mixing_axis)
+        if isinstance(mixing_bin_width, bool) or not isinstance(mixing_bin_width, (numbers.Integral, np.integer)) or mixing_bin_width < 1:
+            solver_error("config", f"mixing_bin_width must be an integer >= 1, got {mixing_bin_width!r}")
+        self.mixing_bin_width = int(mixing_bin_width)
+        if isinstance(mixing_pdf_bins, bool) or not isinstance(mixing_pdf_bins, (numbers.Integral, np.integer)) \
+                or not 0 <= mixing_pdf_bins <= 1024:
+            solver_error("config", f"mixing_pdf_bins must be an integer in [0, 1024], got {mixing_pdf_bins!r}")
+        self.mixing_pdf_bins = int(mixing_pdf_bins)
+        try:
+            good = len(mixing_pdf_range) == 2 and not any(isinstance(c, bool) for c in mixing_pdf_range) and \
+                all(np.isfinite(float(c)) for c in mixing_pdf_range) and float(mixing_pdf_range[0]) < float(mixing_pdf_range[1])
+        except (TypeError, ValueError):
+            good = False
+        if not good:
+            solver_error("config", f"mixing_pdf_range takes two finite values lo < hi, got {mixing_pdf_range!r}")
+        self.mixing_pdf_range = (float(mixing_pdf_range[0]), float(mixing_pdf_range[1]))
+        if not isinstance(mixing_file, str) or not mixing_file or "/" in mixing_file:
+            solver_error("config", f"mixing_file is a file name inside output_dir, got {mixing_file!r}")
+        self.mixing_file = mixing_file
+        if mixing_scalars is not None:
+            if isinstance(mixing_scalars, str) or not all(isinstance(s, str) for s in mixing_scalars) or len(mixing_scalars) == 0 \
+                    or len(set(mixing_scalars)) != len(tuple(mixing_scalars)):
+                solver_error("config", f"mixing_scalars takes a list of distinct scalar names (None for all), got {mixing_scalars!r}")
+            for s in mixing_scalars:
+                if s not in self.scalar_names:
+                    solver_error("config", f"mixing_scalars: no scalar {s!r}: this run carries {self.scalar_names}")
+        self.mixing_scalars = None if mixing_scalars is None else tuple(mixing_scalars)
+        self.state_mixing = self.mixing_step != 0 or self.mixing_at_end         # any mixing sample taken during the run
+        if self.state_mixing and not self.scalar_names:
+            solver_error("config", "mixing_step / mixing_at_end need passive scalars: this run carries none")
+        if self.state_mixing and self.use_MPI:
+            solver_error("config", "mixing_step / mixing_at_end are not supported for ranks of a process group (use_MPI=true): "
+                                   "one block only")
         if isinstance(error_norms_step, bool) or not isinstance(error_norms_step, (numbers.Integral, np.integer)) or error_norms_step < 0:
             solver_error("config", f"error_norms_step must be an integer >= 0, got {error_norms_step!r}")
         self.error_norms_step = int(error_norms_step)

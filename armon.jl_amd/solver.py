@@ -43,6 +43,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     images: list = field(default_factory=list)          # paths of the frames of image_step / image_at_end
     scalars: tuple = ()                                  # names of the run's passive scalars (read with stats.data.scalar(name))
     diffusion_steps: int = 0                             # launches of armon_hip_diffuse: the sub-steps of every cycle
+    mixing: list = field(default_factory=list)          # (cycle, time, {name: mixing.MixingProfile}, {name: mixing.ScalarPDF} or None) of mixing_step / mixing_at_end
 
     def __str__(self):   # ref src/solver.jl:26-35
         return (f"Solver stats:\n - final time:  {self.final_time}\n - last Δt:     {self.last_dt}\n"
@@ -203,6 +204,7 @@ class BlockGrid:
         self.error_norms_taken = []            # (cycle, time, ErrorNorms) of the run's error_norms_step / error_norms_at_end
         self.history = None                    # History of the run's history_step
         self.images = []                       # paths of the frames of the run's image_step / image_at_end
+        self.mixing_samples = []               # (cycle, time, profiles, pdfs) of the run's mixing_step / mixing_at_end
 
     def ptr(self, name):
         return C.c_void_p(self.data[name].ptr)
@@ -456,6 +458,21 @@ class BlockGrid:
         self.params.wait()
         return profile.profile_state([(self.params, self)], kind, bins=bins, width=width, centre=centre, dr=dr, with_p=with_p,
                                      scale_exp=scale_exp)
+
+    def mixing(self, axis="y", width=1, scalars=None, scale_exp=None, bins=None):
+        """The mixing measures of this block's passive scalars along ``axis`` = ``"x" | "y"`` in bins of ``width`` cells,
+        computed on the device (mixing.py states the rule and the arguments) → dict name → ``mixing.MixingProfile``."""
+        from . import mixing
+        self.params.wait()
+        return mixing.mixing_state([(self.params, self)], axis, width=width, scalars=scalars, scale_exp=scale_exp, bins=bins)
+
+    def scalar_pdf(self, name, bins=64, range=(0., 1.), window=None):
+        """The histogram of the passive scalar ``name`` over ``bins`` equal bins of ``range = (lo, hi)``, with the exact mass
+        of every bin, computed on the device (mixing.py) → ``mixing.ScalarPDF``. ``window``: ``(col0, row0, wnx, wny)`` of the
+        real cells to take instead of all of them."""
+        from . import mixing
+        self.params.wait()
+        return mixing.pdf_state([(self.params, self)], name, bins=bins, range=range, windows=None if window is None else [window])
 
     def derive(self, quantities, factor=1, reduce="mean"):
         """Derived flow fields of this block's state — names of ``derived.QUANTITIES`` (rho, p, e, speed, mach, grad_rho,
@@ -1230,6 +1247,8 @@ def graph_cycles_usable(params):
         return False                    # and a history sample enqueued behind a cycle
     if params.state_image:
         return False                    # and an image frame rendered
+    if params.state_mixing:
+        return False                    # and a mixing sample taken
     if params.forced:
         return False                    # and the kick of a body force enqueued behind every cycle (not part of the captured graph)
     if params.diffusive:
@@ -1449,6 +1468,7 @@ def time_loop(params, grid):
     profiled_at, grid.profiles = -1, []   # (and the time of the profiles)
     normed_at, grid.error_norms_taken = -1, []   # (and of the error norms)
     imaged_at, grid.images = -1, []       # (and of the image frames)
+    mixed_at, grid.mixing_samples = -1, []   # (and of the mixing samples; a restart starts a new series)
     hist, dt_used, grid.history = None, 0.0, None
     if params.history_step != 0:
         from .history import HistoryRun
@@ -1493,6 +1513,13 @@ def time_loop(params, grid):
             profile_run(grid, params, gdt)
             save_ns += _time.perf_counter_ns() - t_save
             profiled_at = gdt.cycle
+        if params.mixing_step != 0 and gdt.cycle % params.mixing_step == 0:
+            from .mixing import mixing_run
+            params.wait()
+            t_save = _time.perf_counter_ns()
+            mixing_run(grid, params, gdt)
+            save_ns += _time.perf_counter_ns() - t_save
+            mixed_at = gdt.cycle
         if params.image_step != 0 and gdt.cycle % params.image_step == 0:
             from .derived import image_run
             params.wait()
@@ -1527,6 +1554,9 @@ def time_loop(params, grid):
     if params.profile_at_end and profiled_at != gdt.cycle:
         from .profile import profile_run
         profile_run(grid, params, gdt)
+    if params.mixing_at_end and mixed_at != gdt.cycle:
+        from .mixing import mixing_run
+        mixing_run(grid, params, gdt)
     if params.image_at_end and imaged_at != gdt.cycle:
         from .derived import image_run
         image_run(grid, params, gdt)
@@ -1573,6 +1603,7 @@ def armon(params):
     stats.error_norms = list(grid.error_norms_taken)
     stats.history = grid.history
     stats.images = list(grid.images)
+    stats.mixing = list(grid.mixing_samples)
     stats.scalars = tuple(params.scalar_names)
     stats.diffusion_steps = grid.diffusion_steps
     if params.return_data:

@@ -1078,6 +1078,93 @@ typedef struct armon_diffuse_desc_f32 {
 ARMON_API int armon_hip_diffuse(armon_ctx*, const armon_diffuse_desc*);
 ARMON_API int armon_hip_diffuse_f32(armon_ctx*, const armon_diffuse_desc_f32*);
 
+/* ---- mixing measures: exact binned sums and histograms of the passive scalars (csrc/mixing.hip) ------ */
+/* No reference counterpart. Two passes over rho and the scalar planes, built like armon_hip_profile: every addend is rounded
+ * once to a fixed-point integer, everything after that is integer addition, an unsigned minimum or an unsigned maximum, so
+ * every record below is the merge of the records of the parts of its window, WORD FOR WORD, whatever the split, the launch
+ * shape, the alignment path or the ghost width.
+ *
+ * One (plane, bin) of armon_hip_mixing: 20 words = 160 B. A sum is three signed limbs as in armon_profile_bin: its value is
+ * (sum[j][0] + sum[j][1] 2^32 + sum[j][2] 2^64) 2^s_kj. NO LIMB CAN OVERFLOW WHILE FEWER THAN 2^31 CELLS ARE MERGED INTO ONE
+ * BIN. phi_min / phi_max are order keys as in armon_profile_bin. */
+typedef struct {
+    uint64_t n;             /* cells added                                              (sum) */
+    uint64_t n_bad;         /* cells refused for this plane                             (sum) */
+    int64_t  sum[5][3];     /* rho, phi, phi*phi, rho*phi, rho*phi*phi: three limbs each (sum, limb by limb, no carry) */
+    uint64_t phi_min, phi_max;   /* order keys                                          (min / max) */
+    uint64_t reserved;      /* zero */
+} armon_mixing_bin;
+typedef struct {
+    int32_t axis, reserved;     /* ARMON_PROFILE_X or ARMON_PROFILE_Y; reserved = 0 */
+    int64_t nbins, width;       /* width: cells per bin */
+    int32_t scale_exp[ARMON_MAX_SCALARS][5];   /* s_kj: quantum of sum j of plane k is 2^s_kj, -4096 <= s_kj <= 4096 */
+} armon_mixing_spec;
+
+/* Write the neutral element of the merge into bins_dev[0 .. ns * nbins): zeros, phi_min all ones, phi_max zero. Async. */
+ARMON_API int armon_hip_mixing_reset(armon_ctx*, int ns, int64_t nbins, armon_mixing_bin* bins_dev);
+
+/* MERGE the real cells [col0, col0 + wnx) x [row0, row0 + wny) of one block into bins_dev[plane][bin], plane < ns, bin < nbins.
+ * Block, window, (global_col0, global_row0) and their checks are those of armon_hip_profile. phi: a HOST array of `ns` device
+ * pointers, planes in the layout of the state vectors. Also refused (ARMON_ERR_INVALID_ARG, nothing written): a NULL pointer,
+ * ns outside 1..ARMON_MAX_SCALARS, a NULL plane, nbins < 1, width < 1, an axis other than X or Y, a scale_exp of a plane < ns
+ * outside [-4096, 4096]. `spec` and `phi` are HOST memory, read before the call returns.
+ * Per cell at the global position (gx, gy) and per plane k, all arithmetic in fp64 whatever the data type (fp32 values are
+ * converted first), one IEEE operation per operation written:
+ *   bin    X: b = gx / width.  Y: b = gy / width.  A cell with b >= nbins is skipped and counted nowhere.
+ *   terms  t0 = rho, t1 = phi, t2 = phi * phi, t3 = rho * phi, t4 = t3 * phi.
+ *   Q_j    = round-half-even(t_j / 2^s_kj), an exact integer.
+ *   bad    rho, phi_k or a t_j not finite, or a |Q_j| >= 2^95: the cell adds 1 to n_bad OF PLANE k and nothing else; the
+ *          other planes are not affected.
+ *   limbs  with a = |Q_j|: a & 0xffffffff, (a >> 32) & 0xffffffff, a >> 64, each negated when Q_j < 0, each added to its own
+ *          int64. phi enters phi_min and phi_max through its order key.
+ * No ghost cell is read. Integer atomics only (order-independent: the words are a function of rho, the planes, the spec and
+ * the scale), no scratch, async on the context's stream with no host synchronisation. One launch per plane: the words of a
+ * call with ns planes are those of ns calls with one plane each. The tuning knob PROFILE_WGS caps the workgroups of these
+ * kernels and of armon_hip_scalar_pdf as it does armon_hip_profile's, and changes no result bit. */
+ARMON_API int armon_hip_mixing(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, const double* rho, int ns,
+        const double* const* phi, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_col0,
+        int64_t global_row0, const armon_mixing_spec* spec, armon_mixing_bin* bins_dev);
+ARMON_API int armon_hip_mixing_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, const float* rho, int ns,
+        const float* const* phi, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_col0,
+        int64_t global_row0, const armon_mixing_spec* spec, armon_mixing_bin* bins_dev);
+
+/* Same geometry, spec and checks (scale_exp is not used): bounds_dev[k * 5 + j] = max(bounds_dev[k * 5 + j], bit pattern of the
+ * largest FINITE |t_j| of plane k over the window's cells), as unsigned integers; cells past the last bin count too. */
+ARMON_API int armon_hip_mixing_bounds(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, const double* rho,
+        int ns, const double* const* phi, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_col0,
+        int64_t global_row0, const armon_mixing_spec* spec, uint64_t* bounds_dev);
+ARMON_API int armon_hip_mixing_bounds_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, const float* rho,
+        int ns, const float* const* phi, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, int64_t global_col0,
+        int64_t global_row0, const armon_mixing_spec* spec, uint64_t* bounds_dev);
+
+/* The histogram of one plane: (nbins + 2) rows of 4 words — the cell count (uint64) and the exact sum of rho as three signed
+ * limbs of quantum 2^rho_scale_exp — followed by ONE word, the count of bad cells: 4 (nbins + 2) + 1 words in all. Rows
+ * 0 .. nbins - 1 are the bins, row nbins is "below", row nbins + 1 is "above". Every word merges by integer addition; the
+ * neutral element is all zeros. */
+typedef struct {
+    double  lo, inv_w;          /* the lower edge of bin 0 and 1 / (bin width): both finite, inv_w > 0 */
+    int32_t nbins;              /* 1 .. ARMON_PDF_MAX_BINS */
+    int32_t rho_scale_exp;      /* -4096 .. 4096 */
+} armon_pdf_spec;
+#define ARMON_PDF_MAX_BINS 1024
+
+/* Zero the 4 (nbins + 2) + 1 words of out_dev. Async. */
+ARMON_API int armon_hip_scalar_pdf_reset(armon_ctx*, int nbins, uint64_t* out_dev);
+
+/* MERGE the real cells of the window into out_dev. Geometry and its checks as armon_hip_mixing (the global position is not
+ * part of the rule: no argument for it). Also refused (ARMON_ERR_INVALID_ARG, nothing written): a NULL pointer, nbins outside
+ * 1..ARMON_PDF_MAX_BINS, a lo or inv_w that is not finite, inv_w <= 0, rho_scale_exp outside [-4096, 4096].
+ * Per cell, in fp64 (fp32 values converted first), one IEEE operation per operation written:
+ *   bad    rho or phi not finite, or |Q(rho)| >= 2^95 with Q = round-half-even(rho / 2^rho_scale_exp): the cell adds 1 to the
+ *          bad word and nothing else.
+ *   row    else if phi < lo: "below". Else fb = floor((phi - lo) * inv_w); if !(fb < nbins): "above"; else bin (int64)fb.
+ *   adds   1 to the row's count, the limbs of Q(rho) (cut as in armon_hip_profile) to the row's three limb sums.
+ * Integer atomics only, no scratch, async on the context's stream with no host synchronisation. */
+ARMON_API int armon_hip_scalar_pdf(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, const double* rho,
+        const double* phi, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, const armon_pdf_spec* spec, uint64_t* out_dev);
+ARMON_API int armon_hip_scalar_pdf_f32(armon_ctx*, int64_t row_length, int nghost, int64_t nx, int64_t ny, const float* rho,
+        const float* phi, int64_t col0, int64_t row0, int64_t wnx, int64_t wny, const armon_pdf_spec* spec, uint64_t* out_dev);
+
 
 /* ---- multi-GPU: tile-decomposed grid, halo exchange and dt reduction on the device ------------------------------ */
 /* Replaces the reference's MPI path: start_exchange / finish_exchange (ref src/halo_exchange.jl:229-283), the side
