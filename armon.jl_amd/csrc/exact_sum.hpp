@@ -1,4 +1,5 @@
-// exact_sum.hpp — the fixed-point addends of the decomposition-independent sums (profile.hip, analytic.hip, history.hip).
+// exact_sum.hpp — the fixed-point addends of the decomposition-independent sums (profile.hip and mixing.hip through
+// binned.hpp, analytic.hip, history.hip).
 // A term t is rounded ONCE, on its own, to Q = round-half-even(t / 2^s); |Q| is cut into three limbs below
 // 2^32, each negated when Q < 0 and each added to its own int64. Everything after the rounding is integer addition, so a
 // sum is a function of its addends only, word for word.

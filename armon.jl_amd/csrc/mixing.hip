@@ -18,16 +18,14 @@
 // MERGE: every word merges by integer addition, unsigned minimum or unsigned maximum, so a record is a function of the
 // planes, the spec and the scale only, WORD FOR WORD (profile.hip says why the limbs are kept apart from the first cell on).
 //
-// Launch. The main pass is k_profile's (profile.hip) with two loads per row instead of four and a 19-word record: tiles of one
-// span (64 lanes x 16 B) by 32 rows, walked down the rows of a span for X and along the spans of a row block for Y; a lane
-// sums in registers while its bin does not change, then ds atomics into a table of 264 bins in LDS, then one global 64-bit
-// atomic per word that is not neutral. ONE LAUNCH PER PLANE: a lane holds one record, never ns of them, and the words of a
-// call with ns planes are those of ns calls by construction. rho is read once per plane: 16 ns B per fp64 cell.
-// The bounds pass is the window walk. The PDF pass is the window walk too: a lane keeps a run (row, count, three limbs) and
-// adds it to a table of nbins + 2 rows in LDS when the row changes; the table goes out once, at the end, one global atomic
-// per word that is not zero. Equal rows of neighbouring lanes are not combined before the LDS. No scratch, no host
-// synchronisation, integer atomics only.
-#include "exact_sum.hpp"
+// Launch: binned.hpp states the main pass, the bounds pass and the grid; here two loads per row and a record with one (min, max)
+// pair, phi: 19 words of 20. The tiles go down the rows of a span for X and along the spans of a row block for Y. ONE LAUNCH
+// PER PLANE: a lane holds one record, never ns of them, and the words of a call with ns planes are those of ns calls by
+// construction. rho is read once per plane: 16 ns B per fp64 cell.
+// The PDF pass is the window walk: a lane keeps a run (row, count, three limbs) and adds it to a table of nbins + 2 rows in
+// LDS when the row changes; the table goes out once, at the end, one global atomic per word that is not zero. Equal rows of
+// neighbouring lanes are not combined before the LDS. No scratch, no host synchronisation, integer atomics only.
+#include "binned.hpp"
 
 #include <cmath>
 
@@ -35,16 +33,8 @@ using namespace armon;
 
 namespace {
 
-using win::kWave;
-using win::kWavesPerBlock;
-constexpr int kTileRows = 32, kRowsPerWave = kTileRows / kWavesPerBlock;
-constexpr int kRec = 19;                    // words of a record that are not reserved
-constexpr int kRecWords = 20;               // sizeof(armon_mixing_bin) / 8
-constexpr int kTable = 264;                 // bins of the LDS table: X at width 1 needs a span's worth, 128 (fp64) or 256 (fp32)
-constexpr int W_N = 0, W_BAD = 1, W_SUM = 2, W_PHI_MIN = 17, W_PHI_MAX = 18;
-constexpr int kPdfRowWords = 4;             // count, three limbs
-constexpr int kPdfTable = (ARMON_PDF_MAX_BINS + 2) * kPdfRowWords + 1;
-
+using binned::kTileRows;
+using binned::lane_rec;
 using exact::u64;
 using exact::u128;
 using exact::quantise;
@@ -53,216 +43,65 @@ using win::bits_of;
 using win::finite;
 using win::load_cells;
 using win::wide;
+constexpr int kPairs = 1, kRecWords = 20;   // phi; sizeof(armon_mixing_bin) / 8
+constexpr int kPdfRowWords = 4;             // count, three limbs
+constexpr int kPdfTable = (ARMON_PDF_MAX_BINS + 2) * kPdfRowWords + 1;
 
 static_assert(sizeof(armon_mixing_bin) == kRecWords * 8, "armon_mixing_bin is 20 words");
+static_assert(binned::layout<kPairs>::used == 19, "phi_min, phi_max are words 17 and 18");
 static_assert(sizeof(armon_mixing_spec) == 24 + 20 * ARMON_MAX_SCALARS, "armon_mixing_spec has no padding");
 static_assert(sizeof(armon_pdf_spec) == 24, "armon_pdf_spec is 24 bytes");
 
 template <typename T>
 struct mix_args {
-    const T *rho, *phi;             // one plane per launch
-    win::window w;
-    int64_t nrb;                    // blocks of kTileRows rows
-    int64_t gx0, gy0;               // global position of the window's first cell
+    binned::pass_args<T, 2> p;      // rho and ONE plane per launch
     int64_t nbins, width;
     int scale_exp[5];               // the plane's
-    u64* bins;                      // the plane's [nbins][kRecWords]
-    u64* bounds;                    // the plane's [5] (the bounds pass)
 };
 
-struct lane_rec {
-    u64 n, n_bad;
-    long long sum[5][3];
-    u64 phi_min, phi_max;
-    __device__ __forceinline__ void reset()
+// what binned.hpp asks of a measure
+template <typename T, int AXIS>
+struct measure {
+    static constexpr int NF = 2, NX = kPairs, kRecWords = ::kRecWords;
+    static constexpr bool kAlongRows = AXIS == ARMON_PROFILE_Y;
+    struct place {};
+    const mix_args<T>& a;
+    __device__ __forceinline__ int64_t tile_base(int64_t gxa, int64_t, int64_t gya, int64_t) const
     {
-        n = n_bad = 0;
-#pragma unroll
-        for (int k = 0; k < 5; k++) sum[k][0] = sum[k][1] = sum[k][2] = 0;
-        phi_min = ~0ull;
-        phi_max = 0;
+        return (AXIS == ARMON_PROFILE_X ? gxa : gya) / a.width;     // the smallest bin of the tile
+    }
+    __device__ __forceinline__ int64_t bin(int64_t gx, int64_t gy, place&) const
+    {
+        const int64_t b = (AXIS == ARMON_PROFILE_X ? gx : gy) / a.width;
+        return b < a.nbins ? b : -1;
+    }
+    // the five terms of a cell → false when the cell is bad
+    __device__ __forceinline__ bool terms(const T c[2], const place&, double t[5]) const
+    {
+        const double rho = (double)c[0], phi = (double)c[1];
+        t[0] = rho; t[1] = phi; t[2] = phi * phi; t[3] = rho * phi; t[4] = t[3] * phi;
+        return finite(rho) && finite(phi) && finite(t[2]) && finite(t[3]) && finite(t[4]);
+    }
+    __device__ __forceinline__ void add(const T c[2], const place& pl, lane_rec<kPairs>& acc) const
+    {
+        double t[5];
+        const bool ok = terms(c, pl, t);
+        if (binned::add_terms(t, ok, a.scale_exp, 5, acc)) acc.take(0, order_key(t[1]));
     }
 };
-
-// the five terms of a cell → false when the cell is bad
-template <typename T>
-__device__ __forceinline__ bool cell_terms(T rho_, T phi_, double t[5])
-{
-    const double rho = (double)rho_, phi = (double)phi_;
-    t[0] = rho; t[1] = phi; t[2] = phi * phi; t[3] = rho * phi; t[4] = t[3] * phi;
-    return finite(rho) && finite(phi) && finite(t[2]) && finite(t[3]) && finite(t[4]);
-}
-
-template <typename T>
-__device__ __forceinline__ void add_cell(const int scale_exp[5], T rho, T phi, lane_rec& acc)
-{
-    double t[5];
-    u128 a[5];
-    bool ok = cell_terms<T>(rho, phi, t);
-#pragma unroll
-    for (int k = 0; k < 5; k++) ok = quantise(t[k], scale_exp[k], a[k]) && ok;
-    if (!ok) {
-        acc.n_bad += 1;
-        return;
-    }
-    acc.n += 1;
-#pragma unroll
-    for (int k = 0; k < 5; k++) exact::add_limbs(acc.sum[k], a[k], bits_of(t[k]) >> 63);
-    const u64 key = order_key(t[1]);
-    acc.phi_min = key < acc.phi_min ? key : acc.phi_min;
-    acc.phi_max = key > acc.phi_max ? key : acc.phi_max;
-}
-
-__device__ __forceinline__ void merge_min(u64* dst, u64 v)
-{
-    if (v < __atomic_load_n(dst, __ATOMIC_RELAXED)) atomicMin(dst, v);    // the word only falls: a stale read costs an atomic, no more
-}
-__device__ __forceinline__ void merge_max(u64* dst, u64 v)
-{
-    if (v > __atomic_load_n(dst, __ATOMIC_RELAXED)) atomicMax(dst, v);
-}
-
-// a lane's record into a record in LDS or in bins_dev
-__device__ __forceinline__ void merge_rec(u64* dst, const lane_rec& r)
-{
-    if (r.n_bad) atomicAdd(dst + W_BAD, r.n_bad);
-    if (r.n == 0) return;
-    atomicAdd(dst + W_N, r.n);
-#pragma unroll
-    for (int k = 0; k < 5; k++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            if (r.sum[k][j]) atomicAdd(dst + W_SUM + 3 * k + j, (u64)r.sum[k][j]);
-    merge_min(dst + W_PHI_MIN, r.phi_min);
-    merge_max(dst + W_PHI_MAX, r.phi_max);
-}
 
 template <typename T, bool WIDE, int AXIS>
 __global__ void __launch_bounds__(kBlock, 2)
 k_mixing(mix_args<T> a)
 {
-    constexpr int V = wide<T>::n;
-    __shared__ u64 table[kTable * kRec];
-    __shared__ int table_hi;                                        // the last record of the table written since it last went out
-    const int tid = (int)threadIdx.x, lane = tid & (kWave - 1), w = tid / kWave;
-    for (int i = tid; i < kTable * kRec; i += kBlock) table[i] = i % kRec == W_PHI_MIN ? ~0ull : 0ull;
-    if (tid == 0) table_hi = -1;
-    int64_t table_base = -1;                                        // workgroup-uniform
-    const auto table_out = [&]() {                                  // (between two barriers)
-        const int used = (table_hi + 1) * kRec;
-        __syncthreads();
-        if (tid == 0) table_hi = -1;
-        for (int i = tid; i < used; i += kBlock) {
-            const int word = i % kRec;
-            const u64 v = table[i], neutral = word == W_PHI_MIN ? ~0ull : 0ull;
-            if (v == neutral) continue;
-            u64* dst = a.bins + (table_base + i / kRec) * kRecWords + word;     // only bins < nbins were ever written
-            if (word == W_PHI_MIN) merge_min(dst, v);
-            else if (word == W_PHI_MAX) merge_max(dst, v);
-            else atomicAdd(dst, v);
-            table[i] = neutral;
-        }
-    };
-    lane_rec acc;
-    acc.reset();
-    int64_t cur = -1;                                               // the bin `acc` belongs to
-    const auto lane_out = [&]() {
-        if (cur < 0) return;
-        const int64_t at = cur - table_base;
-        if (at >= 0 && at < kTable) {
-            merge_rec(table + at * kRec, acc);
-            if ((int)at > __atomic_load_n(&table_hi, __ATOMIC_RELAXED)) atomicMax(&table_hi, (int)at);
-        } else {
-            merge_rec(a.bins + cur * kRecWords, acc);
-        }
-        acc.reset();
-        cur = -1;
-    };
-    __syncthreads();
-    const int64_t ntiles = a.w.nspan * a.nrb, per = (ntiles + gridDim.x - 1) / gridDim.x;
-    const int64_t t0 = (int64_t)blockIdx.x * per, t1 = t0 + per < ntiles ? t0 + per : ntiles;
-    const T* __restrict__ rho = a.rho + a.w.first;
-    const T* __restrict__ phi = a.phi + a.w.first;
-    for (int64_t tile = t0; tile < t1; tile++) {
-        const int64_t sp = AXIS == ARMON_PROFILE_Y ? tile % a.w.nspan : tile / a.nrb;
-        const int64_t rb = AXIS == ARMON_PROFILE_Y ? tile / a.w.nspan : tile % a.nrb;
-        const int64_t xa = sp * kWave * V;
-        const int64_t ya = rb * kTileRows, yb = ya + kTileRows < a.w.wny ? ya + kTileRows : a.w.wny;
-        const int64_t base = AXIS == ARMON_PROFILE_X ? (a.gx0 + xa) / a.width : (a.gy0 + ya) / a.width;   // the smallest bin of the tile
-        if (base != table_base) {
-            lane_out();
-            __syncthreads();
-            table_out();
-            __syncthreads();
-            table_base = base;
-        }
-        const auto [x, left] = win::lane_column<V>(a.w, sp, lane);
-        if (left <= 0) continue;                                    // (no barrier below this line of the loop body)
-        for (int i = 0; i < kRowsPerWave; i++) {
-            const int64_t r = ya + (int64_t)w * kRowsPerWave + i;
-            if (r >= yb) break;
-            T fr[V], fp[V];                                         // both loads are issued before the first arithmetic
-            const int64_t at = r * a.w.pitch + x;
-            load_cells<T, WIDE>(rho + at, left >= V, left, fr);
-            load_cells<T, WIDE>(phi + at, left >= V, left, fp);
-#pragma unroll
-            for (int c = 0; c < V; c++) {
-                if (c >= left) break;
-                const int64_t b = (AXIS == ARMON_PROFILE_X ? a.gx0 + x + c : a.gy0 + r) / a.width;
-                if (b >= a.nbins) continue;
-                if (b != cur) {
-                    lane_out();
-                    cur = b;
-                }
-                add_cell<T>(a.scale_exp, fr[c], fp[c], acc);
-            }
-        }
-    }
-    lane_out();
-    __syncthreads();
-    table_out();
+    binned::main_pass<measure<T, AXIS>, T, WIDE>(measure<T, AXIS>{a}, a.p);
 }
 
-// the bounds pass: the bit pattern of the largest finite |t_j| of the window, merged by unsigned maximum
 template <typename T, bool WIDE>
 __global__ void __launch_bounds__(kBlock, 4)
 k_mixing_bounds(mix_args<T> a)
 {
-    constexpr int V = wide<T>::n;
-    __shared__ u64 lds[kWavesPerBlock];
-    const int tid = (int)threadIdx.x;
-    const T* __restrict__ rho = a.rho + a.w.first;
-    const T* __restrict__ phi = a.phi + a.w.first;
-    u64 top[5] = {0, 0, 0, 0, 0};
-    win::walk<V>(a.w, [&](int64_t r, int64_t x, int64_t left) {
-        if (left <= 0) return;
-        T fr[V], fp[V];
-        const int64_t at = r * a.w.pitch + x;
-        load_cells<T, WIDE>(rho + at, left >= V, left, fr);
-        load_cells<T, WIDE>(phi + at, left >= V, left, fp);
-#pragma unroll
-        for (int c = 0; c < V; c++) {
-            if (c >= left) break;
-            double t[5];
-            (void)cell_terms<T>(fr[c], fp[c], t);                   // every cell of the window counts, binned or not
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                const u64 m = bits_of(fabs(t[k]));
-                if (finite(t[k]) && m > top[k]) top[k] = m;
-            }
-        }
-    });
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        const u64 m = red::block_reduce<red::op_umax, kWavesPerBlock>(top[k], lds, tid);
-        if (tid == 0 && m) merge_max(a.bounds + k, m);
-    }
-}
-
-__global__ void k_mixing_reset(int64_t words, u64* __restrict__ bins)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < words) bins[i] = i % kRecWords == W_PHI_MIN ? ~0ull : 0ull;
+    binned::bounds_pass<measure<T, ARMON_PROFILE_X>, T, WIDE>(measure<T, ARMON_PROFILE_X>{a}, a.p);
 }
 
 template <typename T>
@@ -338,22 +177,12 @@ k_scalar_pdf(pdf_args<T> a)
     }
 }
 
-__global__ void k_zero_words(int64_t words, u64* __restrict__ out)
+template <typename T, bool BOUNDS, bool WIDE>
+int launch_axis(armon_ctx* ctx, int axis, int64_t work, const mix_args<T>& a)
 {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < words) out[i] = 0;
-}
-
-// the grid = what is resident at once of the kernel launched, at most `work` workgroups and at most the profile kernels' cap
-template <typename K>
-int resident_blocks(armon_ctx* ctx, K kernel, int64_t work, int64_t& blocks)
-{
-    int per_cu = 0;
-    ARMON_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kBlock, 0));
-    blocks = (int64_t)ctx->n_cu * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
-    if (ctx->tune_profile_wgs > 0 && blocks > ctx->tune_profile_wgs) blocks = ctx->tune_profile_wgs;     // PROFILE_WGS: no result bit changes
-    if (blocks > work) blocks = work;
-    return ARMON_OK;
+    if (BOUNDS) return binned::launch_resident(ctx, k_mixing_bounds<T, WIDE>, work, a);
+    return axis == ARMON_PROFILE_X ? binned::launch_resident(ctx, k_mixing<T, WIDE, ARMON_PROFILE_X>, work, a)
+                                   : binned::launch_resident(ctx, k_mixing<T, WIDE, ARMON_PROFILE_Y>, work, a);
 }
 
 template <typename T, bool BOUNDS>
@@ -366,7 +195,8 @@ int mixing_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
     ARMON_REQUIRE(ns >= 1 && ns <= ARMON_MAX_SCALARS, "mixing: ns = %d leaves 1..%d", ns, ARMON_MAX_SCALARS);
     for (int k = 0; k < ns; k++) ARMON_REQUIRE(phi[k] != nullptr, "mixing: phi[%d] is NULL", k);
     mix_args<T> a;
-    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, a.w);
+    binned::pass_args<T, 2>& p = a.p;
+    int rc = win::make_window<T>(row_length, nghost, nx, ny, col0, row0, wnx, wny, p.w);
     if (rc == ARMON_OK) rc = win::check_global_cell(global_col0, global_row0);
     if (rc != ARMON_OK) return rc;
     const armon_mixing_spec& s = *spec;
@@ -377,55 +207,23 @@ int mixing_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int6
         for (int j = 0; j < 5; j++)
             ARMON_REQUIRE(s.scale_exp[k][j] >= -4096 && s.scale_exp[k][j] <= 4096, "mixing: scale_exp[%d][%d] = %d leaves [-4096, 4096]", k, j,
                           s.scale_exp[k][j]);
-    a.rho = rho;
-    a.nrb = (wny + kTileRows - 1) / kTileRows;
-    a.gx0 = global_col0; a.gy0 = global_row0;
+    p.f[0] = rho;
+    p.nrb = (wny + kTileRows - 1) / kTileRows;
+    p.gx0 = global_col0; p.gy0 = global_row0;
     a.nbins = s.nbins; a.width = s.width;
     uintptr_t mis = (uintptr_t)rho;
     for (int k = 0; k < ns; k++) mis |= (uintptr_t)phi[k];          // one alignment path for the whole call
-    const bool wide_ok = win::rows_are_16B(a.w, mis, wide<T>::n);
-    // the bounds pass: a wave per (row, span) item; the main pass: a workgroup per tile
-    const int64_t work = BOUNDS ? (a.w.wny * a.w.nspan + kWavesPerBlock - 1) / kWavesPerBlock : a.w.nspan * a.nrb;
-    int64_t blocks = 0;
-#define ARMON_MIXING_GRID(KERNEL)                                                       \
-    do {                                                                                \
-        rc = resident_blocks(ctx, KERNEL, work, blocks);                                \
-        if (rc != ARMON_OK) return rc;                                                  \
-    } while (0)
+    const bool wide_ok = win::rows_are_16B(p.w, mis, wide<T>::n);
+    const int64_t work = binned::pass_work(p.w, p.nrb, BOUNDS);
     for (int k = 0; k < ns; k++) {
-        a.phi = phi[k];
+        p.f[1] = phi[k];
         for (int j = 0; j < 5; j++) a.scale_exp[j] = s.scale_exp[k][j];
-        a.bins = BOUNDS ? nullptr : static_cast<u64*>(out_dev) + (int64_t)k * s.nbins * kRecWords;
-        a.bounds = BOUNDS ? static_cast<u64*>(out_dev) + 5 * k : nullptr;
-        if (BOUNDS) {
-            if (wide_ok) {
-                ARMON_MIXING_GRID((k_mixing_bounds<T, true>));
-                hipLaunchKernelGGL((k_mixing_bounds<T, true>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-            } else {
-                ARMON_MIXING_GRID((k_mixing_bounds<T, false>));
-                hipLaunchKernelGGL((k_mixing_bounds<T, false>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-            }
-        } else if (s.axis == ARMON_PROFILE_X) {
-            if (wide_ok) {
-                ARMON_MIXING_GRID((k_mixing<T, true, ARMON_PROFILE_X>));
-                hipLaunchKernelGGL((k_mixing<T, true, ARMON_PROFILE_X>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-            } else {
-                ARMON_MIXING_GRID((k_mixing<T, false, ARMON_PROFILE_X>));
-                hipLaunchKernelGGL((k_mixing<T, false, ARMON_PROFILE_X>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-            }
-        } else {
-            if (wide_ok) {
-                ARMON_MIXING_GRID((k_mixing<T, true, ARMON_PROFILE_Y>));
-                hipLaunchKernelGGL((k_mixing<T, true, ARMON_PROFILE_Y>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-            } else {
-                ARMON_MIXING_GRID((k_mixing<T, false, ARMON_PROFILE_Y>));
-                hipLaunchKernelGGL((k_mixing<T, false, ARMON_PROFILE_Y>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-            }
-        }
-        rc = check_launch(BOUNDS ? "mixing_bounds" : "mixing");
+        p.bins = BOUNDS ? nullptr : static_cast<u64*>(out_dev) + (int64_t)k * s.nbins * kRecWords;
+        p.bounds = BOUNDS ? static_cast<u64*>(out_dev) + 5 * k : nullptr;
+        rc = wide_ok ? launch_axis<T, BOUNDS, true>(ctx, s.axis, work, a) : launch_axis<T, BOUNDS, false>(ctx, s.axis, work, a);
+        if (rc == ARMON_OK) rc = check_launch(BOUNDS ? "mixing_bounds" : "mixing");
         if (rc != ARMON_OK) return rc;
     }
-#undef ARMON_MIXING_GRID
     return ARMON_OK;
 }
 
@@ -447,18 +245,9 @@ int pdf_impl(armon_ctx* ctx, int64_t row_length, int nghost, int64_t nx, int64_t
     a.s = s;
     a.out = reinterpret_cast<u64*>(out_dev);
     const bool wide_ok = win::rows_are_16B(a.w, (uintptr_t)rho | (uintptr_t)phi, wide<T>::n);
-    const int64_t work = (a.w.wny * a.w.nspan + kWavesPerBlock - 1) / kWavesPerBlock;
-    int64_t blocks = 0;
-    if (wide_ok) {
-        rc = resident_blocks(ctx, k_scalar_pdf<T, true>, work, blocks);
-        if (rc != ARMON_OK) return rc;
-        hipLaunchKernelGGL((k_scalar_pdf<T, true>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-    } else {
-        rc = resident_blocks(ctx, k_scalar_pdf<T, false>, work, blocks);
-        if (rc != ARMON_OK) return rc;
-        hipLaunchKernelGGL((k_scalar_pdf<T, false>), dim3((unsigned)blocks), dim3(kBlock), 0, ctx->stream, a);
-    }
-    return check_launch("scalar_pdf");
+    const int64_t work = binned::pass_work(a.w, 0, true);           // a walk, as the bounds passes
+    rc = wide_ok ? binned::launch_resident(ctx, k_scalar_pdf<T, true>, work, a) : binned::launch_resident(ctx, k_scalar_pdf<T, false>, work, a);
+    return rc == ARMON_OK ? check_launch("scalar_pdf") : rc;
 }
 
 }  // namespace
@@ -471,8 +260,7 @@ int armon_hip_mixing_reset(armon_ctx* ctx, int ns, int64_t nbins, armon_mixing_b
     ARMON_REQUIRE(ns >= 1 && ns <= ARMON_MAX_SCALARS && nbins >= 1 && nbins < (1ll << 48) && bins_dev,
                   "mixing_reset: ns = %d, nbins = %lld, bins_dev = %p", ns, (long long)nbins, (void*)bins_dev);
     const int64_t words = (int64_t)ns * nbins * kRecWords;
-    hipLaunchKernelGGL(k_mixing_reset, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, words,
-                       reinterpret_cast<u64*>(bins_dev));
+    binned::launch_reset<kPairs, kRecWords>(ctx, words, bins_dev);
     return check_launch("mixing_reset");
 }
 
@@ -509,8 +297,7 @@ int armon_hip_scalar_pdf_reset(armon_ctx* ctx, int nbins, uint64_t* out_dev)
     ARMON_REQUIRE(ctx != nullptr, "ctx is NULL");
     ARMON_REQUIRE(nbins >= 1 && nbins <= ARMON_PDF_MAX_BINS && out_dev, "scalar_pdf_reset: nbins = %d, out_dev = %p", nbins, (void*)out_dev);
     const int64_t words = (int64_t)(nbins + 2) * kPdfRowWords + 1;
-    hipLaunchKernelGGL(k_zero_words, dim3((unsigned)((words + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, words,
-                       reinterpret_cast<u64*>(out_dev));
+    binned::launch_reset<0, 1>(ctx, words, out_dev);                // (no pairs: every word is neutral at 0)
     return check_launch("scalar_pdf_reset");
 }
 

@@ -31,7 +31,7 @@ from fractions import Fraction
 import numpy as np
 
 from ._lib import MixingSpec, PdfSpec, check, solver_error
-from .profile import MASK, SCALE_LIMIT, default_scale, from_key, from_limbs, order_key, quantise_limbs  # noqa: F401
+from .profile import MASK, SCALE_LIMIT, default_scale, from_key, from_limbs, order_key, order_keys, quantise_limbs  # noqa: F401
 
 AXES = {"x": 0, "y": 1}
 TERMS = ("rho", "phi", "phi2", "rho_phi", "rho_phi2")
@@ -50,11 +50,6 @@ def cell_terms(rho, phi):
     with np.errstate(all="ignore"):
         t3 = rho * phi
         return [rho, phi, phi * phi, t3, t3 * phi]
-
-
-def _keys(a):
-    bits = np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-    return np.where(bits >> np.uint64(63) != 0, ~bits, bits ^ np.uint64(1 << 63))
 
 
 def _signed_limbs(t, s):
@@ -89,7 +84,7 @@ def reference_record(axis, nbins, width, scale_exp, rho, phi, origin=(0, 0)):
     along = (np.arange(nx, dtype=np.int64) + int(origin[0])) if axis == 0 else (np.arange(ny, dtype=np.int64) + int(origin[1]))
     b = along // int(width)                     # the bin of every column (x) or row (y)
     line = 0 if axis == 0 else 1                # the array axis that is summed first: whole columns or whole rows share a bin
-    keys = _keys(t[1])
+    keys = order_keys(t[1])
     raw = neutral(nbins)
     cols = np.zeros((len(along), WORDS), dtype=np.int64)
     cols[:, W_N] = good.sum(axis=line)

@@ -114,6 +114,12 @@ def order_key(x):
     return (b ^ MASK) if b >> 63 else (b ^ (1 << 63))
 
 
+def order_keys(a):
+    """``order_key`` for a whole array (converted to fp64 first) → uint64 array of the same shape."""
+    bits = np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+    return np.where(bits >> np.uint64(63) != 0, ~bits, bits ^ np.uint64(1 << 63))
+
+
 def from_key(k):
     b = (k ^ (1 << 63)) if k >> 63 else (k ^ MASK)
     return float(np.array([b], dtype=np.uint64).view(np.float64)[0])
@@ -163,10 +169,7 @@ def reference_record(kind, nbins, scale_exp, rho, u, v, E, p, origin=(0, 0), ski
     finite = np.ones(nx * ny, dtype=bool)
     for a in fields + [a.ravel() for a in t]:
         finite &= np.isfinite(a)
-    def keys(a):                                # order_key, for a whole array
-        bits = np.ascontiguousarray(a.ravel()).view(np.uint64)
-        return np.where(bits >> np.uint64(63) != 0, ~bits, bits ^ np.uint64(1 << 63)).tolist()
-    key_of = {W_RHO_MIN: keys(t[0]), W_P_MIN: keys(t[4])}
+    key_of = {W_RHO_MIN: order_keys(t[0]).ravel().tolist(), W_P_MIN: order_keys(t[4]).ravel().tolist()}
     b, t = b.ravel(), [a.ravel().tolist() for a in t]
     words = [[0] * WORDS for _ in range(nbins)]
     for w in words:

@@ -135,6 +135,36 @@ def test_exact_when_every_workgroup_walks_many_tiles(test, dtype, kind):
     assert int(P.n.sum()) == BIG[0] * BIG[1]
 
 
+@pytest.mark.parametrize("wgs", [0, 1])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("nghost", [4, 5])
+@pytest.mark.parametrize("test", ["Sedov", "Sod"])
+def test_exact_when_rings_leave_the_lds_table(test, nghost, dtype, wgs):
+    """Rings four times finer than a cell (dr = dx / 4) around an off-centre centre, on 300 x 40: a span of 128 (fp64) or 256
+    (fp32) columns crosses 500 to 1000 rings where the LDS table holds 264, so most lane records go straight to bins_dev
+    (asserted on the bins of every tile below); the default bins skip no cell. nghost 4 takes the 16-B path, 5 the element
+    path. With PROFILE_WGS = 1 one workgroup walks every tile and the table's first bin changes with every tile."""
+    from armon_amd import profile as prof
+    N = (300, 40)
+    grid = state_of(test, N, dtype, nghost=nghost)
+    params = grid.params
+    set_wgs(grid, wgs)
+    try:
+        P = grid.profile("r", centre=off_centre(params), dr=float(params.cell_size(0)) / 4)
+    finally:
+        set_wgs(grid, 0)
+    f = real_fields(grid)
+    # a tile's table starts at or below the tile's smallest bin and holds 264: a cell 264 bins above that is outside it
+    b, _ = prof.cell_terms("r", f["rho"], f["u"], f["v"], f["E"], None, np.arange(N[0])[None, :], np.arange(N[1])[:, None], **geometry(P.spec))
+    span = 128 if dtype == "float64" else 256
+    for y in range(0, N[1], 32):
+        for x in range(0, N[0], span):
+            tile = b[y:y + 32, x:x + span]
+            assert (tile >= tile.min() + 264).any() or tile.shape[1] < 64, (x, y)
+    same_words(P, oracle_record(P, f), (test, nghost, dtype, wgs))
+    assert int(P.n.sum()) == N[0] * N[1] and int(P.n_bad.sum()) == 0
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_windows_knobs_and_repeats_change_no_word(dtype):
     from armon_amd import profile as prof

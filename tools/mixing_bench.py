@@ -93,7 +93,9 @@ def one_type(a, dtype):
         for name, bytes_per_cell in (("mixing", 2 * ns), ("bounds", 2 * ns), ("pdf", 2), ("profile", 4)):
             ms = median(t[name])
             res[f"{name}_ns{ns}_ms"], res[f"{name}_ns{ns}_GBps"] = round(ms, 4), round(bytes_per_cell * cells / ms / 1e6, 1)
-        res[f"mixing_ns{ns}_ms_min"], res[f"mixing_ns{ns}_ms_max"] = round(min(t["mixing"]), 4), round(max(t["mixing"]), 4)
+            res[f"{name}_ns{ns}_ms_min"], res[f"{name}_ns{ns}_ms_max"] = round(min(t[name]), 4), round(max(t[name]), 4)
+        res[f"copy4_ns{ns}_ms"] = round(median(t["copy4"]), 4)
+        res[f"copy4_ns{ns}_ms_min"], res[f"copy4_ns{ns}_ms_max"] = round(min(t["copy4"]), 4), round(max(t["copy4"]), 4)
         res[f"mixing_ns{ns}_per_plane_over_profile"] = round(median(t["mixing"]) / ns / median(t["profile"]), 4)
     p_bins.free()
     copy4 = median(copies)
