@@ -2,10 +2,12 @@
 // as ONE kernel launch: EOS → boundary mirror → fluxes → cell update → advection → projection, reading
 // ρ,u,v,E once and writing them once (64 B per cell instead of the 352 B of the five staged passes),
 // optionally followed by the dt/CFL reduction of the next cycle (ref src/reductions.jl:2-53) on the state
-// it has just produced. This header is the host side: the launch model, the dispatch ladder and the entry point.
+// it has just produced. This header is the host side: the launch model and the entry points (the descriptor checks, the
+// common fill of sweep_args and the ladder from a descriptor to its flavour are sweep_device.hpp's: the scalar sweep shares them).
 //
 // Where the kernels live:
-//  * sweep_device.hpp: sweep_args, boundary and dt-state helpers, buffer addressing, dt/CFL tracking, k_fold_pairs / k_fold_dt.
+//  * sweep_device.hpp: sweep_args, boundary and dt-state helpers, buffer addressing, dt/CFL tracking, k_fold_pairs / k_fold_dt;
+//    host side: check_sweep_desc, base_sweep_args, with_flavour.
 //  * sweep_y_kernel.hpp: Y sweep (k_sweep_y): lane ↔ column (fp32 tuned: two adjacent columns), the register pipeline of
 //    sweep_pipeline.hpp marches along y; optional store exchange through LDS (sweep_args::y_sx).
 //  * sweep_x_kernel.hpp: X sweep, spatial form (k_sweep_x_dpp): lane ↔ cell(s) of a row, neighbours fetched with
@@ -218,29 +220,6 @@ int dispatch_track(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape&
     return launch<PIPE, false>(ctx, a, axis, ys, n_blocks);
 }
 
-template <int SCHEME, int LIM, int PROJ, int EOS>
-int dispatch_exact(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape& ys, bool exact, bool track, int64_t* nb)
-{
-    if (exact) return dispatch_track<fused::Pipe<SCHEME, LIM, PROJ, EOS, real>>(ctx, a, axis, ys, track, nb);
-    return dispatch_track<fused::PipeFast<SCHEME, LIM, PROJ, EOS, real>>(ctx, a, axis, ys, track, nb);
-}
-
-template <int SCHEME, int LIM, int PROJ>
-int dispatch_eos(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape& ys, int eos, bool exact, bool track, int64_t* nb)
-{
-    if (eos == ARMON_EOS_BIZARRIUM)
-        return dispatch_exact<SCHEME, LIM, PROJ, ARMON_EOS_BIZARRIUM>(ctx, a, axis, ys, exact, track, nb);
-    return dispatch_exact<SCHEME, LIM, PROJ, ARMON_EOS_PERFECT_GAS>(ctx, a, axis, ys, exact, track, nb);
-}
-
-template <int SCHEME, int LIM>
-int dispatch_proj(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape& ys, int eos, int proj, bool exact, bool track, int64_t* nb)
-{
-    if (proj == ARMON_PROJECTION_EULER_2ND)
-        return dispatch_eos<SCHEME, LIM, ARMON_PROJECTION_EULER_2ND>(ctx, a, axis, ys, eos, exact, track, nb);
-    return dispatch_eos<SCHEME, LIM, ARMON_PROJECTION_EULER>(ctx, a, axis, ys, eos, exact, track, nb);
-}
-
 }  // namespace
 
 // One sweep of the block `d` describes, reading arrays of pitch `in_len` and writing arrays of pitch `out_len` (cell (x, y) at
@@ -248,27 +227,10 @@ int dispatch_proj(armon_ctx* ctx, const sweep_args& a, int axis, const y_shape& 
 static int sweep_pitched(armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int64_t in_len, int64_t out_len)
 {
     ARMON_REQUIRE(ctx && d, "NULL argument");
-    ARMON_REQUIRE(d->axis == ARMON_AXIS_X || d->axis == ARMON_AXIS_Y, "invalid axis %d", d->axis);
-    ARMON_REQUIRE(d->scheme == ARMON_SCHEME_GODUNOV || d->scheme == ARMON_SCHEME_GAD, "unknown scheme %d", d->scheme);
-    ARMON_REQUIRE(d->projection == ARMON_PROJECTION_EULER || d->projection == ARMON_PROJECTION_EULER_2ND,
-                  "unknown projection %d", d->projection);
-    ARMON_REQUIRE(d->eos == ARMON_EOS_PERFECT_GAS || d->eos == ARMON_EOS_BIZARRIUM, "unknown EOS %d", d->eos);
-    ARMON_REQUIRE(d->scheme != ARMON_SCHEME_GAD || (d->limiter >= ARMON_LIMITER_NONE && d->limiter <= ARMON_LIMITER_SUPERBEE),
-                  "unknown limiter tag %d", d->limiter);
-    ARMON_REQUIRE(d->nx > 0 && d->ny > 0, "empty block %lld x %lld", (long long)d->nx, (long long)d->ny);
-    ARMON_REQUIRE(d->ny < (1ll << 30) && d->nx < (1ll << 30), "block too large (%lld x %lld)", (long long)d->nx, (long long)d->ny);
-    const int lag = (d->scheme == ARMON_SCHEME_GAD ? 1 : 0) + (d->projection == ARMON_PROJECTION_EULER_2ND ? 1 : 0) + 2;
-    ARMON_REQUIRE(d->nghost >= lag, "nghost = %d but this scheme/projection reads %d cells past the block", d->nghost, lag);
-    const int64_t n_axis = d->axis == ARMON_AXIS_X ? d->nx : d->ny;
-    ARMON_REQUIRE(!(d->bc_low || d->bc_high) || n_axis >= lag,
-                  "mirror boundary needs at least %d cells along the sweep axis", lag);
-    // The in-tile mirror scales the velocities of the mirrored cell and evaluates the EOS of the ghost cell from them, where
-    // the reference copies p and c along with the state (ref src/halo_exchange.jl:2-29): the same bits when u² and v² are
-    // unchanged, i.e. for factors of magnitude 1 — the only ones the reference has (ref src/tests.jl:150-161).
-    ARMON_REQUIRE(!d->bc_low || (std::fabs(d->u_factor_low) == 1. && std::fabs(d->v_factor_low) == 1.),
-                  "mirror factors of the low side must be +1 or -1 (got %g, %g)", d->u_factor_low, d->v_factor_low);
-    ARMON_REQUIRE(!d->bc_high || (std::fabs(d->u_factor_high) == 1. && std::fabs(d->v_factor_high) == 1.),
-                  "mirror factors of the high side must be +1 or -1 (got %g, %g)", d->u_factor_high, d->v_factor_high);
+    int lag;
+    if (const int bad = check_sweep_desc(d, &lag); bad != ARMON_OK) return bad;
+    const bool X = d->axis == ARMON_AXIS_X;
+    const int64_t n_axis = X ? d->nx : d->ny;
     ARMON_REQUIRE(d->rho_in && d->u_in && d->v_in && d->E_in && d->rho_out && d->u_out && d->v_out && d->E_out,
                   "NULL state array");
     ARMON_REQUIRE(d->rho_in != d->rho_out && d->u_in != d->u_out && d->v_in != d->v_out && d->E_in != d->E_out,
@@ -283,33 +245,11 @@ static int sweep_pitched(armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int64_t in_l
     // would take `dt` (then a factor) for the step itself, silently
     ARMON_REQUIRE(!d->dt_state || d->x_kernel == 0 || d->x_kernel == 3,
                   "dt_state is not honoured by x_kernel form %d (only the DPP X sweeps and the Y march read it)", d->x_kernel);
-    const bool exact = d->exact != 0;
     const bool track = d->dt_cfl_out != nullptr;
     ARMON_REQUIRE(!track || (d->cfl_dx > 0 && d->cfl_dy > 0), "dt_cfl_out needs cfl_dx, cfl_dy > 0");
 
-    sweep_args a;
-    a.nx = d->nx;
-    a.ny = d->ny;
-    a.row_len = in_len;
-    a.out_len = out_len;
-    a.g = d->nghost;
-    a.bc_low = d->bc_low;
-    a.bc_high = d->bc_high;
+    sweep_args a = base_sweep_args(d, in_len, out_len);
     a.emit = (d->p_out ? 1 : 0) | (d->c_out ? 2 : 0);
-    a.dt = (real)d->dt;
-    a.dx = (real)d->dx;
-    a.gamma = (real)d->gamma;
-    a.inv_dx = real(1) / a.dx;        // IEEE quotients: the bits the kernels' own divisions gave until round 4
-    a.dt_dx = a.dt / a.dx;
-    const bool X = d->axis == ARMON_AXIS_X;
-    a.fa_low = (real)(X ? d->u_factor_low : d->v_factor_low);
-    a.ft_low = (real)(X ? d->v_factor_low : d->u_factor_low);
-    a.fa_high = (real)(X ? d->u_factor_high : d->v_factor_high);
-    a.ft_high = (real)(X ? d->v_factor_high : d->u_factor_high);
-    a.rho_in = d->rho_in;
-    a.ua_in = X ? d->u_in : d->v_in;
-    a.ut_in = X ? d->v_in : d->u_in;
-    a.E_in = d->E_in;
     a.rho_out = d->rho_out;
     a.ua_out = X ? d->u_out : d->v_out;
     a.ut_out = X ? d->v_out : d->u_out;
@@ -385,33 +325,20 @@ static int sweep_pitched(armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int64_t in_l
 
     int64_t n_blocks = 0;
     int rc;
+    auto go = [&](auto fl) { return dispatch_track<typename decltype(fl)::PIPE>(ctx, a, d->axis, ys, track, &n_blocks); };
 #ifdef ARMON_ONLY_HEADLINE   // variant builds for A/B timing (tools/build_variant.sh): one instantiation, seconds to compile
 #ifndef ARMON_ONLY_EOS
 #define ARMON_ONLY_EOS ARMON_EOS_PERFECT_GAS       // -DARMON_ONLY_EOS=ARMON_EOS_BIZARRIUM: the one instantiation is config 5's
 #endif
     ARMON_REQUIRE(d->scheme == ARMON_SCHEME_GAD && d->limiter == ARMON_LIMITER_MINMOD && d->projection == ARMON_PROJECTION_EULER_2ND &&
                   d->eos == ARMON_ONLY_EOS && d->x_kernel == 0, "headline-only variant build");
-    rc = dispatch_exact<ARMON_SCHEME_GAD, ARMON_LIMITER_MINMOD, ARMON_PROJECTION_EULER_2ND, ARMON_ONLY_EOS>(ctx, a, d->axis, ys, exact, track, &n_blocks);
-    if (rc != ARMON_OK || !track) return rc;
-    return fold_dt_launch(ctx, a.partials, n_blocks, (real)d->cfl_dx, (real)d->cfl_dy, d->dt_cfl_out, d->dt_accumulate, d->dt_state);
+    rc = d->exact ? go(flavour<ARMON_SCHEME_GAD, ARMON_LIMITER_MINMOD, ARMON_PROJECTION_EULER_2ND, ARMON_ONLY_EOS, true>{})
+               : go(flavour<ARMON_SCHEME_GAD, ARMON_LIMITER_MINMOD, ARMON_PROJECTION_EULER_2ND, ARMON_ONLY_EOS, false>{});
 #else
-    if (d->scheme == ARMON_SCHEME_GODUNOV) {
-        rc = dispatch_proj<ARMON_SCHEME_GODUNOV, ARMON_LIMITER_NONE>(ctx, a, d->axis, ys, d->eos, d->projection, exact, track, &n_blocks);
-    } else {
-        switch (d->limiter) {
-        case ARMON_LIMITER_MINMOD:
-            rc = dispatch_proj<ARMON_SCHEME_GAD, ARMON_LIMITER_MINMOD>(ctx, a, d->axis, ys, d->eos, d->projection, exact, track, &n_blocks);
-            break;
-        case ARMON_LIMITER_SUPERBEE:
-            rc = dispatch_proj<ARMON_SCHEME_GAD, ARMON_LIMITER_SUPERBEE>(ctx, a, d->axis, ys, d->eos, d->projection, exact, track, &n_blocks);
-            break;
-        default:
-            rc = dispatch_proj<ARMON_SCHEME_GAD, ARMON_LIMITER_NONE>(ctx, a, d->axis, ys, d->eos, d->projection, exact, track, &n_blocks);
-        }
-    }
+    rc = with_flavour(d, go);
+#endif
     if (rc != ARMON_OK || !track) return rc;
     return fold_dt_launch(ctx, a.partials, n_blocks, (real)d->cfl_dx, (real)d->cfl_dy, d->dt_cfl_out, d->dt_accumulate, d->dt_state);
-#endif
 }
 
 extern "C" int ARMON_SWEEP_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d)

@@ -3,14 +3,18 @@
 // A passive scalar is "one more transverse velocity that does not enter the EOS": the Lagrangian phase leaves it alone, it
 // is remapped as ρ·φ and divided by the new ρ. The fused sweeps are out of place, so after armon_hip_sweep the pre-sweep
 // state is still there: this launch reads it again (ρ, u, v, E: 32 B per fp64 cell), redoes the state's EOS → solve → GAD →
-// Lagrange → remap of ρ ONCE, and carries all ns planes through it (16 B per plane and cell). The tuned kernels of
-// armon_hip_sweep are not touched: these are sibling forms.
-//  * X sweep (k_scalar_x): lanes along x, neighbours by the DPP shifts of lane_shift.hpp — ScalarSpatial, the sibling of
-//    SpatialSweep. Tuned flavour: the very stage functions (sweep_stages.hpp, fast::) with φ in the slot of ut; exact
-//    flavour: the formulas of SpatialSweep::run_exact.
-//  * Y sweep (k_scalar_y): lanes along x, a register march in y. The state runs through Pipe / PipeFast as they are (what
-//    only feeds u', v', E' is dead code here and the compiler drops it); ScalarMarch reads the pipeline's rings after each
-//    step and keeps the rings of the planes next to them, with the arithmetic the pipeline applies to its ut.
+// Lagrange → remap of ρ ONCE, and carries all ns planes through it (16 B per plane and cell). Neither direction states the
+// sweep's arithmetic again: both run the state through the forms of armon_hip_sweep with outputs that are not stored (what
+// only feeds u', v', E', p and c is dead code here and the compiler drops it) and add the planes' own remap.
+//  * X sweep (k_scalar_x): lanes along x, neighbours by the DPP shifts of lane_shift.hpp — SpatialSweep<..., NS>
+//    (sweep_spatial.hpp), which remaps the planes one after the other behind the state's projection. Tuned flavour: the very
+//    stage functions (sweep_stages.hpp, fast::) with ρ_lag·φ in the slot of ρ·ut; exact flavour: the quotients of run_exact's
+//    t_vrho / o_v lines.
+//  * Y sweep (k_scalar_y): lanes along x, a register march in y. The state runs through Pipe / PipeFast as they are;
+//    ScalarMarch reads the pipeline's rings after each step and keeps the rings of the planes next to them, with the
+//    arithmetic the pipeline applies to its ut.
+// The host side shares the descriptor checks, the common fill of sweep_args and the ladder with armon_hip_sweep
+// (sweep_device.hpp: check_sweep_desc, base_sweep_args, with_flavour).
 // Not a stand-alone header: scalar_sweep.hip (real = double) and scalar_sweep_f32.hip (real = float) include it.
 #pragma once
 #include "sweep_device.hpp"
@@ -23,249 +27,6 @@ template <int NS>
 struct scalar_planes {
     const real* in[NS];
     real* out[NS];
-};
-
-// ---- spatial form -----------------------------------------------------------------------------------------------------
-template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT, int K, typename T, int NS>
-struct ScalarSpatial {
-    using TR = fused::PipeTraits<SCHEME, LIM, PROJ, EOS>;
-    static constexpr int S = TR::S, W = TR::W, LAG = TR::LAG;
-    using S_ = fused::Strip<K, T>;
-    using Sh = fused::Shifted<K, T>;
-    static __device__ __forceinline__ Sh left_of(const S_& s) { return fused::left_of<0, K, T>(s); }
-    static __device__ __forceinline__ Sh right_of(const S_& s) { return fused::right_of<0, K, T>(s); }
-
-    T dt, dx, gamma, inv_dx, dt_dx;
-
-    __device__ __forceinline__ void run(const S_& rho, const S_& ua, const S_& ut, const S_& E, const S_ (&phi)[NS],
-                                        S_ (&o_phi)[NS]) const
-    {
-        if (EXACT) run_exact(rho, ua, ut, E, phi, o_phi);
-        else run_fast(rho, ua, ut, E, phi, o_phi);
-    }
-
-    // the formulas of SpatialSweep::run_exact: the state up to the Lagrangian ρ and Δx, then ρ and the planes
-    __device__ __forceinline__ void run_exact(const S_& rho, const S_& ua, const S_& ut, const S_& E, const S_ (&phi)[NS],
-                                              S_ (&o_phi)[NS]) const
-    {
-        using Den = xct::Den<T>;
-        const Den d_dx(dx);
-        S_ rc, p;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            T cs;
-            if (EOS == ARMON_EOS_BIZARRIUM) {
-                T g_unused;
-                phys::bizarrium<false>(rho[k], E[k], ua[k], ut[k], p.v[k], cs, g_unused);
-            } else {
-                phys::perfect_gas(gamma, rho[k], E[k], ua[k], ut[k], p.v[k], cs);
-            }
-            rc.v[k] = rho[k] * cs;
-        }
-        const Sh rcL = left_of(rc), uL = left_of(ua), pL = left_of(p);
-        S_ gus;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const T rc_l = rcL[k], rc_r = rc[k];
-            const Den d(rc_l + rc_r);
-            gus.v[k] = d.quo_t(rc_l * uL[k] + rc_r * ua[k] + (pL[k] - p[k]));
-        }
-        S_ fus;
-        if (S == 1) {
-            const Sh rhoL = left_of(rho);
-            const Sh gusL = left_of(gus), gusR = right_of(gus);
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const T r_um = phys::limiter<LIM>(Den(gus[k] - uL[k] + T(1e-6)).quo_t(gusR[k] - ua[k]));
-                const T r_up = phys::limiter<LIM>(Den(ua[k] - gus[k] + T(1e-6)).quo_t(uL[k] - gusL[k]));
-                const T dm_l = rhoL[k] * dx;
-                const T dm_r = rho[k] * dx;
-                const T Dm = (dm_l + dm_r) / 2;
-                const T theta = T(0.5) * (1 - (rcL[k] + rc[k]) / 2 * Den(Dm).quo(dt));
-                fus.v[k] = gus[k] + theta * (r_up * (ua[k] - gus[k]) - r_um * (gus[k] - uL[k]));
-            }
-        } else {
-            fus = gus;
-        }
-        const Sh fusR = right_of(fus);
-        S_ l_rho, dxl;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            const T dm = rho[k] * dx;
-            dxl.v[k] = dx + dt * (fusR[k] - fus[k]);
-            l_rho.v[k] = Den(dxl[k]).quo(dm);
-        }
-        // what every remapped quantity shares: slope ratios, displacement, donor side and reach
-        const Sh rL = left_of(l_rho);
-        S_ r_m, r_p, disp, lf, a0;
-        Sh rR;
-        if (W == 1) {
-            rR = right_of(l_rho);
-            const Sh dxlL = left_of(dxl), dxlR = right_of(dxl);
-            S_ s0;
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                r_m.v[k] = Den(dxl[k] + dxlL[k]).quo(2 * dxl[k]);
-                r_p.v[k] = Den(dxl[k] + dxlR[k]).quo(2 * dxl[k]);
-                s0.v[k] = phys::slope_minmod(rL[k], l_rho[k], rR[k], r_m[k], r_p[k]);
-            }
-            const Sh s0L = left_of(s0), fusL = left_of(fus);
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                disp.v[k] = dt * fus[k];
-                const bool up = disp[k] > 0;
-                const T Dxe = up ? -(dx - dt * fusL[k]) : (dx + dt * fusR[k]);
-                lf.v[k] = Den(2 * (up ? dxlL[k] : dxl[k])).quo(Dxe);
-                a0.v[k] = disp[k] * ((up ? rL[k] : l_rho[k]) - (up ? s0L[k] : s0[k]) * lf[k]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                disp.v[k] = dt * fus[k];
-                a0.v[k] = disp[k] * (disp[k] > 0 ? rL[k] : l_rho[k]);
-            }
-        }
-        const Sh a0R = right_of(a0);
-        S_ t_rho;
-#pragma unroll
-        for (int k = 0; k < K; k++) t_rho.v[k] = d_dx.quo(dxl[k] * l_rho[k] - (a0R[k] - a0[k]));
-#pragma unroll
-        for (int n = 0; n < NS; n++) {
-            S_ q, a;
-#pragma unroll
-            for (int k = 0; k < K; k++) q.v[k] = l_rho[k] * phi[n][k];
-            const Sh qL = left_of(q);
-            if (W == 1) {
-                const Sh qR = right_of(q);
-                S_ s;
-#pragma unroll
-                for (int k = 0; k < K; k++) s.v[k] = phys::slope_minmod(qL[k], q[k], qR[k], r_m[k], r_p[k]);
-                const Sh sL = left_of(s);
-#pragma unroll
-                for (int k = 0; k < K; k++) {
-                    const bool up = disp[k] > 0;
-                    a.v[k] = disp[k] * ((up ? qL[k] : q[k]) - (up ? sL[k] : s[k]) * lf[k]);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < K; k++) a.v[k] = disp[k] * (disp[k] > 0 ? qL[k] : q[k]);
-            }
-            const Sh aR = right_of(a);
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const T t_q = d_dx.quo_t(dxl[k] * l_rho[k] * phi[n][k] - (aR[k] - a[k]));
-                o_phi[n].v[k] = Den(t_rho[k]).quo_t(t_q);
-            }
-        }
-    }
-
-    // SpatialSweep::run_fast with φ in the slot of ut from the Lagrangian update on: the same stage functions, called with
-    // the same operands (what they return for ua and E is not used and costs nothing)
-    __device__ __forceinline__ void run_fast(const S_& rho, const S_& ua, const S_& ut, const S_& E, const S_ (&phi)[NS],
-                                             S_ (&o_phi)[NS]) const
-    {
-        namespace fast = fused::fast;
-        const T gm1 = gamma - T(1.), ggm1 = gamma * (gamma - T(1.));
-        S_ rc, p;
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-            T cs;
-            fast::eos<EOS>(gm1, ggm1, rho[k], ua[k], ut[k], E[k], p.v[k], cs, rc.v[k]);
-        }
-        const Sh rcL = left_of(rc), uL = left_of(ua), pL = left_of(p);
-        S_ gus, gps, src;
-#pragma unroll
-        for (int k = 0; k < K; k++) fast::solve(rcL[k], uL[k], pL[k], rc[k], ua[k], p[k], gus.v[k], gps.v[k], src.v[k]);
-        S_ fus, fps;
-        if (S == 1) {
-            const Sh rhoL = left_of(rho);
-            const Sh gusL = left_of(gus), gpsL = left_of(gps), gusR = right_of(gus), gpsR = right_of(gps);
-#pragma unroll
-            for (int k = 0; k < K; k++)
-                fast::gad<LIM>(dt_dx, rhoL[k], uL[k], pL[k], rho[k], ua[k], p[k], src[k],
-                               gusL[k], gpsL[k], gus[k], gps[k], gusR[k], gpsR[k], fus.v[k], fps.v[k]);
-        } else {
-            fus = gus;
-            fps = gps;
-        }
-        S_ dtu, pu;
-#pragma unroll
-        for (int k = 0; k < K; k++) fast::flux_products(dt, fus[k], fps[k], dtu.v[k], pu.v[k]);
-        const Sh dtuR = right_of(dtu), fpsR = right_of(fps), puR = right_of(pu);
-        S_ l_rho, dxl, hinv, q[NS];
-#pragma unroll
-        for (int k = 0; k < K; k++) {
-#pragma unroll
-            for (int n = 0; n < NS; n++) {
-                const fast::Lag<T> l = fast::lagrange(dx, dt_dx, rho[k], ua[k], phi[n][k], E[k], fps[k], dtu[k], pu[k],
-                                                      fpsR[k], dtuR[k], puR[k]);
-                dxl.v[k] = l.dxl;
-                hinv.v[k] = l.hinv;
-                l_rho.v[k] = l.rho;
-                q[n].v[k] = l.q_ut;
-            }
-        }
-        const Sh rL = left_of(l_rho);
-        S_ r_m, r_p, lf, a0;
-        if (W == 1) {
-            const Sh rR = right_of(l_rho);
-            const Sh dxlL = left_of(dxl);
-            S_ isum;
-#pragma unroll
-            for (int k = 0; k < K; k++) isum.v[k] = fast::inv_pair_length(dxl[k], dxlL[k]);
-            const Sh isumR = right_of(isum);
-            S_ s0;
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                r_m.v[k] = fast::slope_ratio(dxl[k], isum[k]);
-                r_p.v[k] = fast::slope_ratio(dxl[k], isumR[k]);
-                s0.v[k] = fast::slope(r_p[k], rR[k], l_rho[k], r_m[k], rL[k]);
-            }
-            const Sh s0L = left_of(s0);
-            const Sh dtuL = left_of(dtu), hinvL = left_of(hinv);
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const T disp = dtu[k];
-                const bool up = disp > 0;
-                const T Dxe = up ? fast::extent_up(dtuL[k], dx) : fast::extent_dn(dx, dtuR[k]);
-                lf.v[k] = fast::donor_reach(Dxe, up ? hinvL[k] : hinv[k]);
-                a0.v[k] = fast::advect2(disp, lf[k], -(up ? s0L[k] : s0[k]), up ? rL[k] : l_rho[k]);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < K; k++) a0.v[k] = fast::advect1(dtu[k], dtu[k] > 0 ? rL[k] : l_rho[k]);
-        }
-        const Sh a0R = right_of(a0);
-#pragma unroll
-        for (int n = 0; n < NS; n++) {
-            S_ a;
-            const Sh qL = left_of(q[n]);
-            if (W == 1) {
-                const Sh qR = right_of(q[n]);
-                S_ s;
-#pragma unroll
-                for (int k = 0; k < K; k++) s.v[k] = fast::slope(r_p[k], qR[k], q[n][k], r_m[k], qL[k]);
-                const Sh sL = left_of(s);
-#pragma unroll
-                for (int k = 0; k < K; k++) {
-                    const bool up = dtu[k] > 0;
-                    a.v[k] = fast::advect2(dtu[k], lf[k], -(up ? sL[k] : s[k]), up ? qL[k] : q[n][k]);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < K; k++) a.v[k] = fast::advect1(dtu[k], dtu[k] > 0 ? qL[k] : q[n][k]);
-            }
-            const Sh aR = right_of(a);
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                // the plane in the slot of ρ·ut; the other two slots are not used
-                const T qq[4] = {l_rho[k], q[n][k], q[n][k], q[n][k]};
-                const T al[4] = {a0[k], a[k], a[k], a[k]}, ah[4] = {a0R[k], aR[k], aR[k], aR[k]};
-                T o_rho, o_u, o_E;
-                fast::project(inv_dx, dxl[k], qq, al, ah, o_rho, o_u, o_phi[n].v[k], o_E);
-            }
-        }
-    }
 };
 
 // ---- march form: the planes' rings next to those of Pipe / PipeFast ---------------------------------------------------
@@ -381,7 +142,7 @@ __global__ void __launch_bounds__(64 * kSXRows)
 k_scalar_x(sweep_args a, scalar_planes<NS> ph, int vec)
 {
     constexpr int K = 2, HALO = 4, WIDTH = 64 * K, STRIDE = WIDTH - 2 * HALO;
-    using SW = ScalarSpatial<SCHEME, LIM, PROJ, EOS, EXACT, K, real, NS>;
+    using SW = fused::SpatialSweep<SCHEME, LIM, PROJ, EOS, EXACT, K, real, 0, NS>;
     using St = fused::Strip<K, real>;
     static_assert(SW::LAG <= HALO, "strip halo");
     const int lane = threadIdx.x;
@@ -423,7 +184,8 @@ k_scalar_x(sweep_args a, scalar_planes<NS> ph, int vec)
         }
     }
     const SW sw{a.dt, a.dx, a.gamma, a.inv_dx, a.dt_dx};
-    sw.run(st[0], st[1], st[2], st[3], phi, o_phi);
+    St unused[6];                                              // ρ', ua', ut', E', p, c: never stored
+    sw.run(st[0], st[1], st[2], st[3], unused[0], unused[1], unused[2], unused[3], unused[4], unused[5], phi, o_phi);
     const int64_t hi = (w0 + STRIDE < a.o_hi) ? w0 + STRIDE : a.o_hi;
     const int64_t lo = w0 > a.o_lo ? w0 : a.o_lo;
     if (vec && j0 >= lo && j0 + 1 < hi) {
@@ -565,7 +327,7 @@ int scalar_y_seg(int n_cu, int64_t nx, int64_t ny)
     return (int)seg;
 }
 
-template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT, int NS>
+template <class FL, int NS>
 int scalar_launch(armon_ctx* ctx, const sweep_args& a, int axis, const real* const* phi_in, real* const* phi_out, bool vec)
 {
     scalar_planes<NS> ph;
@@ -574,48 +336,16 @@ int scalar_launch(armon_ctx* ctx, const sweep_args& a, int axis, const real* con
         ph.out[n] = phi_out[n];
     }
     if (axis == ARMON_AXIS_Y) {
-        using PIPE = typename std::conditional<EXACT, fused::Pipe<SCHEME, LIM, PROJ, EOS, real>,
-                                               fused::PipeFast<SCHEME, LIM, PROJ, EOS, real>>::type;
         const dim3 grid((unsigned)((a.nx + a.xshift + kSYBlock - 1) / kSYBlock), (unsigned)((a.o_hi - a.o_lo + a.seg - 1) / a.seg));
-        hipLaunchKernelGGL((k_scalar_y<PIPE, NS>), grid, dim3(kSYBlock), 0, ctx->stream, a, ph);
+        hipLaunchKernelGGL((k_scalar_y<typename FL::PIPE, NS>), grid, dim3(kSYBlock), 0, ctx->stream, a, ph);
         return check_launch("scalar_y");
     }
     const int64_t groups = (a.ny + kSXRows - 1) / kSXRows;
     const unsigned gy = (unsigned)(groups < 32768 ? groups : 32768);
     const dim3 grid((unsigned)((a.o_hi - a.x_first + 119) / 120), gy, (unsigned)((groups + gy - 1) / gy));
-    hipLaunchKernelGGL((k_scalar_x<SCHEME, LIM, PROJ, EOS, EXACT, NS>), grid, dim3(64, kSXRows), 0, ctx->stream, a, ph, vec ? 1 : 0);
+    hipLaunchKernelGGL((k_scalar_x<FL::SCHEME, FL::LIM, FL::PROJ, FL::EOS, FL::EXACT, NS>), grid, dim3(64, kSXRows), 0, ctx->stream, a, ph,
+                       vec ? 1 : 0);
     return check_launch("scalar_x");
-}
-
-template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT>
-int scalar_ns(armon_ctx* ctx, const sweep_args& a, int axis, int ns, const real* const* in, real* const* out, bool vec)
-{
-    switch (ns) {
-    case 1: return scalar_launch<SCHEME, LIM, PROJ, EOS, EXACT, 1>(ctx, a, axis, in, out, vec);
-    case 2: return scalar_launch<SCHEME, LIM, PROJ, EOS, EXACT, 2>(ctx, a, axis, in, out, vec);
-    case 3: return scalar_launch<SCHEME, LIM, PROJ, EOS, EXACT, 3>(ctx, a, axis, in, out, vec);
-    default: return scalar_launch<SCHEME, LIM, PROJ, EOS, EXACT, 4>(ctx, a, axis, in, out, vec);
-    }
-}
-
-template <int SCHEME, int LIM, int PROJ>
-int scalar_eos(armon_ctx* ctx, const sweep_args& a, int axis, int eos, bool exact, int ns, const real* const* in, real* const* out, bool vec)
-{
-    if (eos == ARMON_EOS_BIZARRIUM) {
-        if (exact) return scalar_ns<SCHEME, LIM, PROJ, ARMON_EOS_BIZARRIUM, true>(ctx, a, axis, ns, in, out, vec);
-        return scalar_ns<SCHEME, LIM, PROJ, ARMON_EOS_BIZARRIUM, false>(ctx, a, axis, ns, in, out, vec);
-    }
-    if (exact) return scalar_ns<SCHEME, LIM, PROJ, ARMON_EOS_PERFECT_GAS, true>(ctx, a, axis, ns, in, out, vec);
-    return scalar_ns<SCHEME, LIM, PROJ, ARMON_EOS_PERFECT_GAS, false>(ctx, a, axis, ns, in, out, vec);
-}
-
-template <int SCHEME, int LIM>
-int scalar_proj(armon_ctx* ctx, const sweep_args& a, int axis, int proj, int eos, bool exact, int ns, const real* const* in,
-                real* const* out, bool vec)
-{
-    if (proj == ARMON_PROJECTION_EULER_2ND)
-        return scalar_eos<SCHEME, LIM, ARMON_PROJECTION_EULER_2ND>(ctx, a, axis, eos, exact, ns, in, out, vec);
-    return scalar_eos<SCHEME, LIM, ARMON_PROJECTION_EULER>(ctx, a, axis, eos, exact, ns, in, out, vec);
 }
 
 }  // namespace
@@ -625,26 +355,10 @@ extern "C" int ARMON_SCALARS_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int n
     ARMON_REQUIRE(ctx && d, "NULL argument");
     ARMON_REQUIRE(ns >= 1 && ns <= ARMON_MAX_SCALARS, "ns = %d: a launch carries 1 to %d scalar planes", ns, ARMON_MAX_SCALARS);
     ARMON_REQUIRE(phi_in && phi_out, "phi_in / phi_out: NULL array of planes");
-    // ---- what armon_hip_sweep refuses -------------------------------------------------------------------------------
-    ARMON_REQUIRE(d->axis == ARMON_AXIS_X || d->axis == ARMON_AXIS_Y, "invalid axis %d", d->axis);
-    ARMON_REQUIRE(d->scheme == ARMON_SCHEME_GODUNOV || d->scheme == ARMON_SCHEME_GAD, "unknown scheme %d", d->scheme);
-    ARMON_REQUIRE(d->projection == ARMON_PROJECTION_EULER || d->projection == ARMON_PROJECTION_EULER_2ND,
-                  "unknown projection %d", d->projection);
-    ARMON_REQUIRE(d->eos == ARMON_EOS_PERFECT_GAS || d->eos == ARMON_EOS_BIZARRIUM, "unknown EOS %d", d->eos);
-    ARMON_REQUIRE(d->scheme != ARMON_SCHEME_GAD || (d->limiter >= ARMON_LIMITER_NONE && d->limiter <= ARMON_LIMITER_SUPERBEE),
-                  "unknown limiter tag %d", d->limiter);
-    ARMON_REQUIRE(d->nx > 0 && d->ny > 0, "empty block %lld x %lld", (long long)d->nx, (long long)d->ny);
-    ARMON_REQUIRE(d->ny < (1ll << 30) && d->nx < (1ll << 30), "block too large (%lld x %lld)", (long long)d->nx, (long long)d->ny);
-    const int lag = (d->scheme == ARMON_SCHEME_GAD ? 1 : 0) + (d->projection == ARMON_PROJECTION_EULER_2ND ? 1 : 0) + 2;
-    ARMON_REQUIRE(d->nghost >= lag, "nghost = %d but this scheme/projection reads %d cells past the block", d->nghost, lag);
+    int lag;
+    if (const int bad = check_sweep_desc(d, &lag); bad != ARMON_OK) return bad;
     const bool X = d->axis == ARMON_AXIS_X;
     const int64_t n_axis = X ? d->nx : d->ny;
-    ARMON_REQUIRE(!(d->bc_low || d->bc_high) || n_axis >= lag,
-                  "mirror boundary needs at least %d cells along the sweep axis", lag);
-    ARMON_REQUIRE(!d->bc_low || (std::fabs(d->u_factor_low) == 1. && std::fabs(d->v_factor_low) == 1.),
-                  "mirror factors of the low side must be +1 or -1 (got %g, %g)", d->u_factor_low, d->v_factor_low);
-    ARMON_REQUIRE(!d->bc_high || (std::fabs(d->u_factor_high) == 1. && std::fabs(d->v_factor_high) == 1.),
-                  "mirror factors of the high side must be +1 or -1 (got %g, %g)", d->u_factor_high, d->v_factor_high);
     ARMON_REQUIRE(d->rho_in && d->u_in && d->v_in && d->E_in, "NULL state array (rho_in, u_in, v_in, E_in: the pre-sweep state)");
     // ---- what only the scalar sweep refuses -------------------------------------------------------------------------
     ARMON_REQUIRE(d->x_kernel == 0, "x_kernel = %d: the scalar sweep has one X form", d->x_kernel);
@@ -663,53 +377,26 @@ extern "C" int ARMON_SCALARS_FN(armon_ctx* ctx, const ARMON_SWEEP_DESC* d, int n
             ARMON_REQUIRE((const void*)phi_out[k] != state[j], "phi_out[%d] aliases a state array of the descriptor", k);
     }
 
-    sweep_args a;
-    a.nx = d->nx;
-    a.ny = d->ny;
-    a.row_len = a.out_len = d->nx + 2 * (int64_t)d->nghost;
-    a.g = d->nghost;
-    a.bc_low = d->bc_low;
-    a.bc_high = d->bc_high;
-    a.emit = 0;
-    a.dt = (real)d->dt;
-    a.dx = (real)d->dx;
-    a.gamma = (real)d->gamma;
-    a.inv_dx = real(1) / a.dx;
-    a.dt_dx = a.dt / a.dx;
-    a.fa_low = (real)(X ? d->u_factor_low : d->v_factor_low);
-    a.ft_low = (real)(X ? d->v_factor_low : d->u_factor_low);
-    a.fa_high = (real)(X ? d->u_factor_high : d->v_factor_high);
-    a.ft_high = (real)(X ? d->v_factor_high : d->u_factor_high);
-    a.rho_in = d->rho_in;
-    a.ua_in = X ? d->u_in : d->v_in;
-    a.ut_in = X ? d->v_in : d->u_in;
-    a.E_in = d->E_in;
-    a.rho_out = a.ua_out = a.ut_out = a.E_out = a.p_out = a.c_out = nullptr;
-    a.partials = nullptr;
-    a.st = nullptr;
-    a.x_kernel = 0;
-    a.o_lo = 0;
+    const int64_t pitch = d->nx + 2 * (int64_t)d->nghost;
+    sweep_args a = base_sweep_args(d, pitch, pitch);
     a.o_hi = n_axis;
     a.seg = X ? 512 : scalar_y_seg(ctx->n_cu, d->nx, d->ny);
     ARMON_REQUIRE(X || a.row_len * (int64_t)sizeof(real) * (a.seg + 2 * lag + 16) < (1ll << 32),
                   "block too wide for 32-bit row offsets (%lld cells per row, runs of %d rows)", (long long)d->nx, a.seg);
     a.xshift = X ? 0 : d->nghost % 16;
     a.x_first = X ? -(int64_t)(d->nghost % 8) : 0;
-    a.xcd_remap = 0;
     // 16-B accesses of the X sweep: every lane pair on an even cell of an even-pitched row, in arrays that start on 16 B
     uintptr_t bases = (uintptr_t)d->rho_in | (uintptr_t)d->u_in | (uintptr_t)d->v_in | (uintptr_t)d->E_in;
     for (int k = 0; k < ns; k++) bases |= (uintptr_t)phi_in[k] | (uintptr_t)phi_out[k];
     const bool vec = X && a.row_len % 2 == 0 && bases % (2 * sizeof(real)) == 0;
 
-    const bool exact = d->exact != 0;
-    if (d->scheme == ARMON_SCHEME_GODUNOV)
-        return scalar_proj<ARMON_SCHEME_GODUNOV, ARMON_LIMITER_NONE>(ctx, a, d->axis, d->projection, d->eos, exact, ns, phi_in, phi_out, vec);
-    switch (d->limiter) {
-    case ARMON_LIMITER_MINMOD:
-        return scalar_proj<ARMON_SCHEME_GAD, ARMON_LIMITER_MINMOD>(ctx, a, d->axis, d->projection, d->eos, exact, ns, phi_in, phi_out, vec);
-    case ARMON_LIMITER_SUPERBEE:
-        return scalar_proj<ARMON_SCHEME_GAD, ARMON_LIMITER_SUPERBEE>(ctx, a, d->axis, d->projection, d->eos, exact, ns, phi_in, phi_out, vec);
-    default:
-        return scalar_proj<ARMON_SCHEME_GAD, ARMON_LIMITER_NONE>(ctx, a, d->axis, d->projection, d->eos, exact, ns, phi_in, phi_out, vec);
-    }
+    return with_flavour(d, [&](auto fl) {
+        using FL = decltype(fl);
+        switch (ns) {
+        case 1: return scalar_launch<FL, 1>(ctx, a, d->axis, phi_in, phi_out, vec);
+        case 2: return scalar_launch<FL, 2>(ctx, a, d->axis, phi_in, phi_out, vec);
+        case 3: return scalar_launch<FL, 3>(ctx, a, d->axis, phi_in, phi_out, vec);
+        default: return scalar_launch<FL, 4>(ctx, a, d->axis, phi_in, phi_out, vec);
+        }
+    });
 }

@@ -1,5 +1,7 @@
 // sweep_device.hpp — what the fused sweep's kernels share: sweep_args, the boundary / dt-state helpers, buffer addressing
-// and its cache policy, the dt/CFL tracking and its fold kernels. Not a stand-alone header (see fused_sweep.hpp).
+// and its cache policy, the dt/CFL tracking and its fold kernels; and what the host sides of armon_hip_sweep and
+// armon_hip_sweep_scalars share: the descriptor checks (check_sweep_desc), the common fill of sweep_args (base_sweep_args)
+// and the ladder from a descriptor to its flavour (with_flavour). Not a stand-alone header (see fused_sweep.hpp).
 #pragma once
 #include "common.hpp"
 #include "dt_state.hpp"
@@ -291,6 +293,101 @@ int fold_dt_launch(armon_ctx* ctx, real* partials, int64_t n, real dx, real dy, 
     }
     hipLaunchKernelGGL(k_fold_dt, dim3(1), dim3(256), 0, ctx->stream, partials, n, dx, dy, out, accumulate, st);
     return check_launch("fold_dt");
+}
+
+// ---- host side: what armon_hip_sweep and armon_hip_sweep_scalars both do with a descriptor ----------------------------------
+// What both refuse, from the axis through the mirror factors (each then checks its own arrays). *lag: cells the
+// scheme / projection reads past a cell.
+int check_sweep_desc(const ARMON_SWEEP_DESC* d, int* lag_out)
+{
+    ARMON_REQUIRE(d->axis == ARMON_AXIS_X || d->axis == ARMON_AXIS_Y, "invalid axis %d", d->axis);
+    ARMON_REQUIRE(d->scheme == ARMON_SCHEME_GODUNOV || d->scheme == ARMON_SCHEME_GAD, "unknown scheme %d", d->scheme);
+    ARMON_REQUIRE(d->projection == ARMON_PROJECTION_EULER || d->projection == ARMON_PROJECTION_EULER_2ND,
+                  "unknown projection %d", d->projection);
+    ARMON_REQUIRE(d->eos == ARMON_EOS_PERFECT_GAS || d->eos == ARMON_EOS_BIZARRIUM, "unknown EOS %d", d->eos);
+    ARMON_REQUIRE(d->scheme != ARMON_SCHEME_GAD || (d->limiter >= ARMON_LIMITER_NONE && d->limiter <= ARMON_LIMITER_SUPERBEE),
+                  "unknown limiter tag %d", d->limiter);
+    ARMON_REQUIRE(d->nx > 0 && d->ny > 0, "empty block %lld x %lld", (long long)d->nx, (long long)d->ny);
+    ARMON_REQUIRE(d->ny < (1ll << 30) && d->nx < (1ll << 30), "block too large (%lld x %lld)", (long long)d->nx, (long long)d->ny);
+    const int lag = (d->scheme == ARMON_SCHEME_GAD ? 1 : 0) + (d->projection == ARMON_PROJECTION_EULER_2ND ? 1 : 0) + 2;
+    *lag_out = lag;
+    ARMON_REQUIRE(d->nghost >= lag, "nghost = %d but this scheme/projection reads %d cells past the block", d->nghost, lag);
+    const int64_t n_axis = d->axis == ARMON_AXIS_X ? d->nx : d->ny;
+    ARMON_REQUIRE(!(d->bc_low || d->bc_high) || n_axis >= lag,
+                  "mirror boundary needs at least %d cells along the sweep axis", lag);
+    // The in-tile mirror scales the velocities of the mirrored cell and evaluates the EOS of the ghost cell from them, where
+    // the reference copies p and c along with the state (ref src/halo_exchange.jl:2-29): the same bits when u² and v² are
+    // unchanged, i.e. for factors of magnitude 1 — the only ones the reference has (ref src/tests.jl:150-161).
+    ARMON_REQUIRE(!d->bc_low || (std::fabs(d->u_factor_low) == 1. && std::fabs(d->v_factor_low) == 1.),
+                  "mirror factors of the low side must be +1 or -1 (got %g, %g)", d->u_factor_low, d->v_factor_low);
+    ARMON_REQUIRE(!d->bc_high || (std::fabs(d->u_factor_high) == 1. && std::fabs(d->v_factor_high) == 1.),
+                  "mirror factors of the high side must be +1 or -1 (got %g, %g)", d->u_factor_high, d->v_factor_high);
+    return ARMON_OK;
+}
+
+// sweep_args of a checked descriptor with what every sweep sets: the block, the step, the mirrors (axial / transverse by the
+// sweep axis) and the arrays it reads, of pitch `in_len`; it writes rows of `out_len`. Everything else is zero / null.
+sweep_args base_sweep_args(const ARMON_SWEEP_DESC* d, int64_t in_len, int64_t out_len)
+{
+    sweep_args a{};
+    a.nx = d->nx;
+    a.ny = d->ny;
+    a.row_len = in_len;
+    a.out_len = out_len;
+    a.g = d->nghost;
+    a.bc_low = d->bc_low;
+    a.bc_high = d->bc_high;
+    a.dt = (real)d->dt;
+    a.dx = (real)d->dx;
+    a.gamma = (real)d->gamma;
+    a.inv_dx = real(1) / a.dx;        // IEEE quotients: the bits the kernels' own divisions gave until round 4
+    a.dt_dx = a.dt / a.dx;
+    const bool X = d->axis == ARMON_AXIS_X;
+    a.fa_low = (real)(X ? d->u_factor_low : d->v_factor_low);
+    a.ft_low = (real)(X ? d->v_factor_low : d->u_factor_low);
+    a.fa_high = (real)(X ? d->u_factor_high : d->v_factor_high);
+    a.ft_high = (real)(X ? d->v_factor_high : d->u_factor_high);
+    a.rho_in = d->rho_in;
+    a.ua_in = X ? d->u_in : d->v_in;
+    a.ut_in = X ? d->v_in : d->u_in;
+    a.E_in = d->E_in;
+    return a;
+}
+
+// The flavour a descriptor selects, as a type; PIPE: its marching pipeline.
+template <int SCHEME_, int LIM_, int PROJ_, int EOS_, bool EXACT_>
+struct flavour {
+    static constexpr int SCHEME = SCHEME_, LIM = LIM_, PROJ = PROJ_, EOS = EOS_;
+    static constexpr bool EXACT = EXACT_;
+    using PIPE = typename std::conditional<EXACT, fused::Pipe<SCHEME, LIM, PROJ, EOS, real>,
+                                           fused::PipeFast<SCHEME, LIM, PROJ, EOS, real>>::type;
+};
+
+// The ladder: f(flavour<...>{}) of a checked descriptor's scheme, limiter (Godunov has none), projection, EOS, arithmetic.
+template <class F>
+int with_flavour(const ARMON_SWEEP_DESC* d, F&& f)
+{
+    using std::integral_constant;
+    auto by_exact = [&](auto s, auto l, auto p, auto e) {
+        if (d->exact) return f(flavour<s.value, l.value, p.value, e.value, true>{});
+        return f(flavour<s.value, l.value, p.value, e.value, false>{});
+    };
+    auto by_eos = [&](auto s, auto l, auto p) {
+        if (d->eos == ARMON_EOS_BIZARRIUM) return by_exact(s, l, p, integral_constant<int, ARMON_EOS_BIZARRIUM>{});
+        return by_exact(s, l, p, integral_constant<int, ARMON_EOS_PERFECT_GAS>{});
+    };
+    auto by_proj = [&](auto s, auto l) {
+        if (d->projection == ARMON_PROJECTION_EULER_2ND) return by_eos(s, l, integral_constant<int, ARMON_PROJECTION_EULER_2ND>{});
+        return by_eos(s, l, integral_constant<int, ARMON_PROJECTION_EULER>{});
+    };
+    const integral_constant<int, ARMON_SCHEME_GAD> gad;
+    if (d->scheme == ARMON_SCHEME_GODUNOV)
+        return by_proj(integral_constant<int, ARMON_SCHEME_GODUNOV>{}, integral_constant<int, ARMON_LIMITER_NONE>{});
+    switch (d->limiter) {
+    case ARMON_LIMITER_MINMOD: return by_proj(gad, integral_constant<int, ARMON_LIMITER_MINMOD>{});
+    case ARMON_LIMITER_SUPERBEE: return by_proj(gad, integral_constant<int, ARMON_LIMITER_SUPERBEE>{});
+    default: return by_proj(gad, integral_constant<int, ARMON_LIMITER_NONE>{});
+    }
 }
 
 }  // namespace

@@ -16,6 +16,15 @@
 // results into Strips; it takes differences and the reciprocal of the right-hand sum of lengths from the neighbouring
 // lane where the march keeps them from the previous step, and evaluates only the chosen donor's operands.
 // Exact flavour: run_exact states its arithmetic itself, like Pipe (sweep_pipeline.hpp says why).
+//
+// Passive scalars (NS > 0; scalar_sweep.hpp's k_scalar_x): the sweep carries NS planes φ_n behind the state,
+// as ScalarMarch carries them beside Pipe in Y. A plane is "one more ut": q = ρ_lag·φ takes the slope, the advection flux and
+// the projection of ρ·ut, with the operations of that line. Everything about the planes stands in `if constexpr (NS > 0)`;
+// with NS = 0 no line of the sweep depends on them. The planes are remapped ONE AFTER THE OTHER, behind the state's
+// projection, from what they share with ρ (slope ratios, donor reach and — exact flavour — the displacement, kept in Strips
+// under NS > 0 only; the tuned displacement dtu and the fluxes of ρ are there anyway): remapping them inside the state's own
+// loops keeps every plane's q, slope and flux alive next to the state's four, which cost a prototype's fp64 ns = 4 kernels
+// 40-50 VGPRs and two to three waves per SIMD (profiles/scalar_unify_resources.txt).
 #pragma once
 
 #include "lane_shift.hpp"
@@ -26,7 +35,8 @@ namespace fused {
 
 // One X sweep of the K cells held by each lane. In: pre-sweep (ρ, u, v, E). Out: post-sweep state, valid
 // for the cells at least LAG cells away from both ends of the wave's strip; p/c: EOS of the cells.
-template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT, int K, typename T = double, int ROW = 0>
+// NS > 0: also the planes phi[0..NS) → o_phi[0..NS), valid for the same cells.
+template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT, int K, typename T = double, int ROW = 0, int NS = 0>
 struct SpatialSweep {
     using TR = PipeTraits<SCHEME, LIM, PROJ, EOS>;
     static constexpr int S = TR::S, W = TR::W, LAG = TR::LAG;
@@ -43,15 +53,17 @@ struct SpatialSweep {
     T inv_dx, dt_dx;
 
     __device__ __forceinline__ void run(const S_& rho, const S_& u, const S_& v, const S_& E,
-                                        S_& o_rho, S_& o_u, S_& o_v, S_& o_E, S_& p, S_& cs) const
+                                        S_& o_rho, S_& o_u, S_& o_v, S_& o_E, S_& p, S_& cs,
+                                        const S_* phi = nullptr, S_* o_phi = nullptr) const
     {
-        if (EXACT) run_exact(rho, u, v, E, o_rho, o_u, o_v, o_E, p, cs);
-        else run_fast(rho, u, v, E, o_rho, o_u, o_v, o_E, p, cs);
+        if (EXACT) run_exact(rho, u, v, E, o_rho, o_u, o_v, o_E, p, cs, phi, o_phi);
+        else run_fast(rho, u, v, E, o_rho, o_u, o_v, o_E, p, cs, phi, o_phi);
     }
 
     // ---------------------------------------------------------------------------------------------
     __device__ __forceinline__ void run_exact(const S_& rho, const S_& ua, const S_& ut, const S_& E,
-                                              S_& o_rho, S_& o_u, S_& o_v, S_& o_E, S_& p, S_& cs) const
+                                              S_& o_rho, S_& o_u, S_& o_v, S_& o_E, S_& p, S_& cs,
+                                              const S_* phi = nullptr, S_* o_phi = nullptr) const
     {
         using Den = xct::Den<T>;       // correctly rounded quotients, shared denominators (sweep_pipeline.hpp)
         const Den d_dx(dx);
@@ -115,6 +127,7 @@ struct SpatialSweep {
         }
         // advection flux on the low side of each cell
         S_ a0, a1, a2, a3;    // ρ, ρu, ρv, ρE
+        [[maybe_unused]] S_ k_rm, k_rp, k_disp, k_lf;     // NS > 0: what the planes share with ρ
         const Sh rL = left_of(l_rho), quL = left_of(q_ua), qvL = left_of(q_ut), qEL = left_of(q_E);
         if (W == 1) {
             const Sh rR = right_of(l_rho), quR = right_of(q_ua), qvR = right_of(q_ut), qER = right_of(q_E);
@@ -128,6 +141,10 @@ struct SpatialSweep {
                 s1.v[k] = phys::slope_minmod(quL[k], q_ua[k], quR[k], r_m, r_p);
                 s2.v[k] = phys::slope_minmod(qvL[k], q_ut[k], qvR[k], r_m, r_p);
                 s3.v[k] = phys::slope_minmod(qEL[k], q_E[k], qER[k], r_m, r_p);
+                if constexpr (NS > 0) {
+                    k_rm.v[k] = r_m;
+                    k_rp.v[k] = r_p;
+                }
             }
             const Sh s0L = left_of(s0), s1L = left_of(s1), s2L = left_of(s2), s3L = left_of(s3);
             const Sh fusL = left_of(fus);
@@ -141,6 +158,10 @@ struct SpatialSweep {
                 a1.v[k] = disp * ((up ? quL[k] : q_ua[k]) - (up ? s1L[k] : s1[k]) * lf);
                 a2.v[k] = disp * ((up ? qvL[k] : q_ut[k]) - (up ? s2L[k] : s2[k]) * lf);
                 a3.v[k] = disp * ((up ? qEL[k] : q_E[k]) - (up ? s3L[k] : s3[k]) * lf);
+                if constexpr (NS > 0) {
+                    k_disp.v[k] = disp;
+                    k_lf.v[k] = lf;
+                }
             }
         } else {
 #pragma unroll
@@ -151,6 +172,7 @@ struct SpatialSweep {
                 a1.v[k] = disp * (up ? quL[k] : q_ua[k]);
                 a2.v[k] = disp * (up ? qvL[k] : q_ut[k]);
                 a3.v[k] = disp * (up ? qEL[k] : q_E[k]);
+                if constexpr (NS > 0) k_disp.v[k] = disp;
             }
         }
         // projection (ref src/projection_schemes.jl:23-41)
@@ -168,11 +190,43 @@ struct SpatialSweep {
             o_v.v[k] = d_rho.quo_t(t_vrho);
             o_E.v[k] = d_rho.quo(t_Erho);
         }
+        // the planes, one after the other: the t_vrho / o_v lines with φ for ut
+        if constexpr (NS > 0) {
+#pragma unroll
+            for (int n = 0; n < NS; n++) {
+                S_ q, a;
+#pragma unroll
+                for (int k = 0; k < K; k++) q.v[k] = l_rho[k] * phi[n][k];
+                const Sh qL = left_of(q);
+                if (W == 1) {
+                    const Sh qR = right_of(q);
+                    S_ s;
+#pragma unroll
+                    for (int k = 0; k < K; k++) s.v[k] = phys::slope_minmod(qL[k], q[k], qR[k], k_rm[k], k_rp[k]);
+                    const Sh sL = left_of(s);
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        const bool up = k_disp[k] > 0;
+                        a.v[k] = k_disp[k] * ((up ? qL[k] : q[k]) - (up ? sL[k] : s[k]) * k_lf[k]);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; k++) a.v[k] = k_disp[k] * (k_disp[k] > 0 ? qL[k] : q[k]);
+                }
+                const Sh aR = right_of(a);
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const T t_q = d_dx.quo_t(dxl[k] * l_rho[k] * phi[n][k] - (aR[k] - a[k]));
+                    o_phi[n].v[k] = Den(o_rho[k]).quo_t(t_q);
+                }
+            }
+        }
     }
 
     // ---------------------------------------------------------------------------------------------
     __device__ __forceinline__ void run_fast(const S_& rho, const S_& ua, const S_& ut, const S_& E,
-                                             S_& o_rho, S_& o_u, S_& o_v, S_& o_E, S_& p, S_& cs) const
+                                             S_& o_rho, S_& o_u, S_& o_v, S_& o_E, S_& p, S_& cs,
+                                             const S_* phi = nullptr, S_* o_phi = nullptr) const
     {
         const T gm1 = gamma - T(1.), ggm1 = gamma * (gamma - T(1.));
         S_ rc;
@@ -211,6 +265,7 @@ struct SpatialSweep {
             q_E.v[k] = n.q_E;
         }
         S_ a0, a1, a2, a3;
+        [[maybe_unused]] S_ k_rm, k_rp, k_lf;     // NS > 0: what the planes share with ρ
         const Sh rL = left_of(l_rho), quL = left_of(q_ua), qvL = left_of(q_ut), qEL = left_of(q_E);
         if (W == 1) {
             const Sh rR = right_of(l_rho), quR = right_of(q_ua), qvR = right_of(q_ut), qER = right_of(q_E);
@@ -230,6 +285,10 @@ struct SpatialSweep {
                 s1.v[k] = fast::slope(r_p, quR[k], q_ua[k], r_m, quL[k]);
                 s2.v[k] = fast::slope(r_p, qvR[k], q_ut[k], r_m, qvL[k]);
                 s3.v[k] = fast::slope(r_p, qER[k], q_E[k], r_m, qEL[k]);
+                if constexpr (NS > 0) {
+                    k_rm.v[k] = r_m;
+                    k_rp.v[k] = r_p;
+                }
             }
             const Sh s0L = left_of(s0), s1L = left_of(s1), s2L = left_of(s2), s3L = left_of(s3);
             const Sh dtuL = left_of(dtu), hinvL = left_of(hinv);
@@ -243,6 +302,7 @@ struct SpatialSweep {
                 a1.v[k] = fast::advect2(disp, lf, -(up ? s1L[k] : s1[k]), up ? quL[k] : q_ua[k]);
                 a2.v[k] = fast::advect2(disp, lf, -(up ? s2L[k] : s2[k]), up ? qvL[k] : q_ut[k]);
                 a3.v[k] = fast::advect2(disp, lf, -(up ? s3L[k] : s3[k]), up ? qEL[k] : q_E[k]);
+                if constexpr (NS > 0) k_lf.v[k] = lf;
             }
         } else {
 #pragma unroll
@@ -261,6 +321,39 @@ struct SpatialSweep {
             const T q[4] = {l_rho[k], q_ua[k], q_ut[k], q_E[k]};
             const T a[4] = {a0[k], a1[k], a2[k], a3[k]}, aR[4] = {a0R[k], a1R[k], a2R[k], a3R[k]};
             fast::project(inv_dx, dxl[k], q, a, aR, o_rho.v[k], o_u.v[k], o_v.v[k], o_E.v[k]);
+        }
+        // the planes, one after the other: the stages of ρ·ut with q = ρ_lag·φ (fast::lagrange's q_ut) in its slot
+        if constexpr (NS > 0) {
+#pragma unroll
+            for (int n = 0; n < NS; n++) {
+                S_ q, a;
+#pragma unroll
+                for (int k = 0; k < K; k++) q.v[k] = l_rho[k] * phi[n][k];
+                const Sh qL = left_of(q);
+                if (W == 1) {
+                    const Sh qR = right_of(q);
+                    S_ s;
+#pragma unroll
+                    for (int k = 0; k < K; k++) s.v[k] = fast::slope(k_rp[k], qR[k], q[k], k_rm[k], qL[k]);
+                    const Sh sL = left_of(s);
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        const bool up = dtu[k] > 0;
+                        a.v[k] = fast::advect2(dtu[k], k_lf[k], -(up ? sL[k] : s[k]), up ? qL[k] : q[k]);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; k++) a.v[k] = fast::advect1(dtu[k], dtu[k] > 0 ? qL[k] : q[k]);
+                }
+                const Sh aR = right_of(a);
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const T qq[4] = {l_rho[k], q[k], q[k], q[k]};            // the other two slots are not used
+                    const T al[4] = {a0[k], a[k], a[k], a[k]}, ah[4] = {a0R[k], aR[k], aR[k], aR[k]};
+                    T t_rho, t_u, t_E;
+                    fast::project(inv_dx, dxl[k], qq, al, ah, t_rho, t_u, o_phi[n].v[k], t_E);
+                }
+            }
         }
     }
 };

@@ -14,7 +14,7 @@ import random
 import numpy as np
 import pytest
 
-from scalars_harness import Planes, assert_untouched, case_numbers, descriptor, kappa_of_plane, lag_of, launch, rand_planes
+from scalars_harness import WALLS, Planes, assert_untouched, case_numbers, descriptor, kappa_of_plane, lag_of, launch, rand_planes
 from scalars_restated import restated_sweep, run_cycles
 from sweep_harness import F_HIGH, F_LOW, MARKER, bits, block_cache
 from sweep_reference import STATE, rand_state, real_mask
@@ -172,6 +172,52 @@ def test_tuned_scalar_sweep(blocks, dtype, axis, shape, scheme, limiter, project
             print(f"\n{dtype} {'XY'[axis]} {nx}x{ny} {scheme} {projection} {eos}: plane {k} {r:.2f} eps of the field maximum "
                   f"(kappa {kappa[k]:.2f}: {r / kappa[k]:.2f} of it, bound 4 kappa)")
             assert r <= 4 * kappa[k], (k, r, kappa[k])
+    finally:
+        P.free()
+
+
+TUNED_CONFIGS = [("GAD", "minmod", "euler_2nd", "perfect_gas"), ("Godunov", "minmod", "euler", "bizarrium")]
+# X: odd pitch (the clamped scalar-access path, a partial last strip and row group); the 16-B path with more than one strip; the
+# smallest block of the configuration (None: LAG x LAG). Y: partial lane group, more than one run.
+TUNED_PLANE_SHAPES = [(0, (123, 5), 5), (0, (250, 9), 4), (0, None, 4), (1, (70, 101), 5)]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("scheme,limiter,projection,eos", TUNED_CONFIGS, ids=lambda v: v)
+@pytest.mark.parametrize("axis,shape,g", TUNED_PLANE_SHAPES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_tuned_planes_do_not_depend_on_their_company(blocks, axis, shape, g, scheme, limiter, projection, eos, dtype):
+    """Tuned arithmetic: plane k of an ns = 4 launch is, bit for bit, the ns = 1 launch on that plane; and in the same ns = 4
+    launch the plane that holds the state's transverse velocity is the transverse velocity armon_hip_sweep writes (mirrors
+    whose transverse factor is +1, as in test_tuned_scalar_sweep)."""
+    nx, ny = shape if shape is not None else (lag_of(scheme, projection),) * 2
+    seed = 777 + nx
+    blk = blocks(nx, ny, g, dtype)
+    opts = (axis, scheme, limiter, projection, eos)
+    f = rand_state(nx, ny, g, eos, dtype, seed)
+    t_name = "v" if axis == 0 else "u"
+    planes = [f[t_name]] + rand_planes(nx, ny, g, 3, dtype, seed + 1)
+    dt, _ = case_numbers(nx, ny, axis, eos, dtype)
+    inside = real_mask(nx, ny, g, axis)
+    mark = MARKER[blk.dtype.name]
+    P = Planes(blk, 4)
+    try:
+        blk.upload(f)
+        blk.mark_outputs()
+        P.upload(planes)
+        d = descriptor(blk, *opts, False, dt, **WALLS)
+        launch(blk, d, P.inp, P.out)
+        _, got = P.fetch()
+        assert_untouched(blk, f, "tuned scalar sweep")
+        for k in range(4):
+            assert ((bits(got[k]) == mark) == ~inside).all(), f"phi_out[{k}]: not exactly the real cells were written"
+        for k in range(4):
+            P.out[0].copy_from_host(blk.marker)
+            launch(blk, d, [P.inp[k]], [P.out[0]])
+            blk.dev.wait()
+            assert np.array_equal(bits(P.out[0].to_host()), bits(got[k])), f"plane {k}: ns = 1 and ns = 4 differ"
+        blk.sweep(*opts, False, dt, **WALLS)               # the state sweep of the same descriptor
+        state = blk.fetch()
+        assert np.array_equal(bits(got[0])[inside], bits(state[t_name])[inside]), "the plane of ut is not the sweep's ut"
     finally:
         P.free()
 
