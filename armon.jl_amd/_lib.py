@@ -278,6 +278,7 @@ SIGNATURES = {
     "armon_hip_choose_placement": (_ci, [_vp, C.POINTER(SweepDesc), C.POINTER(SweepDesc), C.POINTER(_vp), _ci,
                                          C.c_size_t, _ci, _dbl, C.POINTER(_ci * 8), C.POINTER(_dbl), C.POINTER(_ci)]),
     "armon_hip_sweep_scalars": (_ci, [_vp, C.POINTER(SweepDesc), _ci, C.POINTER(_dp), C.POINTER(_dp)]),
+    "armon_hip_sweep_scalars_bounded": (_ci, [_vp, C.POINTER(SweepDesc), _ci, C.POINTER(_dp), C.POINTER(_dp)]),
     "armon_hip_diffuse": (_ci, [_vp, C.POINTER(DiffuseDesc)]),
     "armon_hip_mixing_reset": (_ci, [_vp, _ci, _i64, _dp]),
     "armon_hip_mixing": (_ci, [_vp, _i64, _ci, _i64, _i64, _dp, _ci, C.POINTER(_dp)] + [_i64] * 6 + [C.POINTER(MixingSpec), _dp]),
@@ -339,6 +340,7 @@ def _add_f32_signatures():
         SIGNATURES["armon_hip_" + name + "_f32"] = SIGNATURES["armon_hip_" + name]
     SIGNATURES["armon_hip_sweep_f32"] = SIGNATURES["armon_hip_sweep"]
     SIGNATURES["armon_hip_sweep_scalars_f32"] = SIGNATURES["armon_hip_sweep_scalars"]
+    SIGNATURES["armon_hip_sweep_scalars_bounded_f32"] = SIGNATURES["armon_hip_sweep_scalars_bounded"]
     SIGNATURES["armon_hip_diffuse_f32"] = SIGNATURES["armon_hip_diffuse"]
     SIGNATURES["armon_hip_state_compare_f32"] = SIGNATURES["armon_hip_state_compare"]     # the tolerances stay doubles
     SIGNATURES["armon_hip_derive_f32"] = SIGNATURES["armon_hip_derive"]

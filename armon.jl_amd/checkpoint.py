@@ -191,6 +191,8 @@ def _check_header(header, path):
         if not (isinstance(d, dict) and _is_hexfloat(d.get("nu")) and _is_hexfloat(d.get("chi")) and isinstance(d.get("scalars"), dict)
                 and all(isinstance(k, str) and _is_hexfloat(v) for k, v in d["scalars"].items())):
             bad(f"diffusion = {d!r}")
+    if "scalar_transport" in header and not (header["scalar_transport"] == "bounded" and "scalars" in header):
+        bad(f"scalar_transport = {header['scalar_transport']!r}")       # (the default rule is not written)
     if ("initial_mass" in header or "initial_energy" in header) and not (
             _is_hexfloat(header.get("initial_mass")) and _is_hexfloat(header.get("initial_energy"))):
         bad("initial_mass / initial_energy")
@@ -217,7 +219,18 @@ def bit_options(params):
     if getattr(params, "diffusive", False):     # a run with physical diffusion: likewise
         from .problem import diffusion_description
         options.update(diffusion=diffusion_description(params.viscosity, params.heat_diffusivity, params.scalars))
+    transport = getattr(params, "scalar_transport", "remap")
+    if transport != "remap":                    # scalars carried by another rule than the default: likewise
+        options.update(scalar_transport=transport)
     return options
+
+
+def check_same_transport(params, header, what):
+    """A configuration error when ``header`` (a missing key = ``"remap"``) and the run disagree on the rule the sweeps carry the
+    passive scalars with: the planes of one rule are not the planes of the other."""
+    theirs, mine = header.get("scalar_transport", "remap"), getattr(params, "scalar_transport", "remap")
+    if theirs != mine:
+        solver_error("config", f"{what} was written with scalar_transport = {theirs!r}, this run has scalar_transport = {mine!r}")
 
 
 def check_same_diffusion(params, header, what):
@@ -258,6 +271,7 @@ def check_compatible(params, header, path):
     check_same_gravity(params, header, f"the checkpoint {path}")      # (first: a problem's digest holds its force too)
     check_same_scalars(params, header, f"the checkpoint {path}")      # (and its scalars)
     check_same_diffusion(params, header, f"the checkpoint {path}")    # (and its diffusion coefficients)
+    check_same_transport(params, header, f"the checkpoint {path}")    # (and the rule its scalars are carried with)
     for k in BIT_FIELDS + PROBLEM_FIELDS:
         if header.get(k) != mine.get(k):
             solver_error("config", f"the checkpoint {path} was written with {k} = {header.get(k)!r}, this run has "

@@ -561,6 +561,7 @@ def compare_state(tiles, ref, rtol=None, atol=0.0, names=None, limit=20, band_ro
         checkpoint.check_same_periodic(p0, header, f"the checkpoint {ref}")     # and so is one under other boundaries
         checkpoint.check_same_scalars(p0, header, f"the checkpoint {ref}")      # and the planes of other scalars are other fields
         checkpoint.check_same_diffusion(p0, header, f"the checkpoint {ref}")    # and a state under other diffusion coefficients
+        checkpoint.check_same_transport(p0, header, f"the checkpoint {ref}")    # and planes carried by another transport rule
         theirs = tuple(header["planes"])
     else:
         header, others = None, _tiles_of(ref)
@@ -569,6 +570,7 @@ def compare_state(tiles, ref, rtol=None, atol=0.0, names=None, limit=20, band_ro
         checkpoint.check_same_periodic(p0, checkpoint.bit_options(others[0][0]), "the other grid")
         checkpoint.check_same_scalars(p0, checkpoint.bit_options(others[0][0]), "the other grid")
         checkpoint.check_same_diffusion(p0, checkpoint.bit_options(others[0][0]), "the other grid")
+        checkpoint.check_same_transport(p0, checkpoint.bit_options(others[0][0]), "the other grid")
         theirs = checkpoint.plane_names(others[0][0])
     if names is None:
         names = tuple(f for f in checkpoint.plane_names(p0) if f in theirs)

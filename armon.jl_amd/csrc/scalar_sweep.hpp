@@ -23,6 +23,15 @@ namespace {
 
 [[maybe_unused]] constexpr auto kNoFoldHere = &fold_dt_launch;     // (sweep_device.hpp's dt/CFL fold: nothing is tracked here)
 
+// The planes' transport rule of this translation unit: scalar_sweep*.hip leave it at the remap of ρ·φ,
+// scalar_sweep_bounded*.hip (armon_hip_sweep_scalars_bounded) choose φ per unit mass. Everything else — the checks, the
+// launch geometry, the state's part of the kernels — is the same text.
+#ifndef ARMON_SCALARS_TRANSPORT
+#define ARMON_SCALARS_TRANSPORT 0
+#endif
+constexpr int kTransport = ARMON_SCALARS_TRANSPORT;
+static_assert(kTransport == fused::kTransportRemap || kTransport == fused::kTransportBounded, "transport rule");
+
 template <int NS>
 struct scalar_planes {
     const real* in[NS];
@@ -33,14 +42,16 @@ struct scalar_planes {
 // step<PH8>() is called right after pipe.advance<Y_AXIS, PH8>() and reads what that step left in the pipeline's rings: the
 // Lagrangian cells l[], the final fluxes, the sums of lengths, the advection fluxes of ρ. pc[n][slot]: φ_n of the cell in slot
 // `slot` of the pipeline's cell ring (the caller's prefetch lands there). Returns φ_n of the cell the step emits.
-template <class PIPE, int NS>
+// TRANSPORT: kTransportRemap — the above; kTransportBounded — φ per unit mass: rings of φ (not of q), of its
+// plain minmod slopes σ and of the fluxes A = a_ρ·φ*, with the pipeline's own mass fluxes a[..][0] and Lagrangian cells.
+template <class PIPE, int NS, int TRANSPORT = fused::kTransportRemap>
 struct ScalarMarch {
     using T = typename PIPE::real;
     static constexpr int S = PIPE::S, W = PIPE::W, LAG = PIPE::LAG;
-    T lphi[NS][4];        // exact: φ of the Lagrangian cells cu, cu-1, cu-2 (the pipeline's Upd::ut)
-    T q[NS][4];           // ρ_lag·φ of those cells
-    T d[NS][4];           // tuned: q(this) - q(previous cell) (the pipeline's Upd::d_ut)
-    T s[NS][2];           // limited slopes of cells cu-1 / cu-2
+    T lphi[NS][4];        // exact, and bounded: φ of the Lagrangian cells cu, cu-1, cu-2, cu-3 (the pipeline's Upd::ut)
+    T q[NS][4];           // remap: ρ_lag·φ of those cells
+    T d[NS][4];           // remap, tuned: q(this) - q(previous cell) (the pipeline's Upd::d_ut)
+    T s[NS][2];           // limited slopes of cells cu-1 / cu-2 (remap: of q; bounded: σ of φ)
     T a[NS][2];           // advection fluxes at interfaces na / na-1
 
     __device__ __forceinline__ ScalarMarch()
@@ -55,6 +66,78 @@ struct ScalarMarch {
 
     template <int PH8>
     __device__ __forceinline__ void step(const PIPE& p, const T (&pc)[NS][8], T (&out)[NS])
+    {
+        if constexpr (TRANSPORT == fused::kTransportBounded) step_bounded<PH8>(p, pc, out);
+        else step_remap<PH8>(p, pc, out);
+    }
+
+    // φ per unit mass. Interface na is the low side of cell cu-1 (W = 1; donor cu-2 when it moves up, else cu-1) or of cell
+    // cu (donor cu-1, else cu); the step emits the cell below it, whose neighbours are the ring's slots on either side.
+    template <int PH8>
+    __device__ __forceinline__ void step_bounded(const PIPE& p, const T (&pc)[NS][8], T (&out)[NS])
+    {
+        constexpr int PH = PH8 & 3;
+        constexpr int R0 = PH & 3, R1 = (PH - 1) & 3, R2 = (PH - 2) & 3, R3 = (PH - 3) & 3;
+        constexpr int P0 = PH & 1, P1 = P0 ^ 1;
+        constexpr int CC = (S == 1) ? ((PH8 - 2) & 7) : ((PH8 - 1) & 7);     // the cell the step updated (cu)
+        constexpr int LO = (W == 1) ? R2 : R1, LB = (W == 1) ? R3 : R2, LA = (W == 1) ? R1 : R0;   // emitted, below, above
+        const auto& l1 = p.l[R1];
+        const auto& l2 = p.l[R2];
+        const auto& lo = p.l[LO];
+        const T a_rho = p.a[P0][0];
+#pragma unroll
+        for (int n = 0; n < NS; n++) lphi[n][R0] = pc[n][CC];
+        if constexpr (PIPE::kExact) {
+            using Den = xct::Den<T>;
+            if (W == 1) {
+                const bool up = p.dt * p.fus[R2] > 0;
+                const T nu = Den(up ? l2.dxl.b * l2.rho : l1.dxl.b * l1.rho).quo_t(phys::abs_(a_rho));
+                const T h = T(0.5) * (1 - nu);
+#pragma unroll
+                for (int n = 0; n < NS; n++) {
+                    s[n][P0] = phys::slope_minmod(lphi[n][R2], lphi[n][R1], lphi[n][R0], T(1.), T(1.));
+                    a[n][P0] = a_rho * (up ? lphi[n][R2] + s[n][P1] * h : lphi[n][R1] - s[n][P0] * h);
+                }
+            } else {
+                const bool up = p.dt * p.fus[R1] > 0;
+#pragma unroll
+                for (int n = 0; n < NS; n++) a[n][P0] = a_rho * (up ? lphi[n][R1] : lphi[n][R0]);
+            }
+            const T m = lo.dxl.b * lo.rho;
+            const Den d_rho(p.d_dx.quo(m - (a_rho - p.a[P1][0])));
+#pragma unroll
+            for (int n = 0; n < NS; n++) {
+                const T t_q = p.d_dx.quo_t(m * lphi[n][LO] - (a[n][P0] - a[n][P1]));
+                const T v = d_rho.quo_t(t_q);
+                const T f_lo = phys::mn(phys::mn(lphi[n][LB], lphi[n][LO]), lphi[n][LA]);
+                const T f_hi = phys::mx(phys::mx(lphi[n][LB], lphi[n][LO]), lphi[n][LA]);
+                out[n] = v < f_lo ? f_lo : (v > f_hi ? f_hi : v);
+            }
+        } else {
+            namespace fast = fused::fast;
+            if (W == 1) {
+                const auto up = p.dtu[R2] > T(0.);
+                const T h = fast::leaving_weight(a_rho, fast::inv_mass(fast::sel(up, l2.dxl * l2.rho, l1.dxl * l1.rho)));
+#pragma unroll
+                for (int n = 0; n < NS; n++) {
+                    s[n][P0] = fast::minmod(lphi[n][R0] - lphi[n][R1], lphi[n][R1] - lphi[n][R2]);
+                    a[n][P0] = fast::carry2(a_rho, h, fast::sel(up, s[n][P1], -s[n][P0]), fast::sel(up, lphi[n][R2], lphi[n][R1]));
+                }
+            } else {
+                const auto up = p.dtu[R1] > T(0.);
+#pragma unroll
+                for (int n = 0; n < NS; n++) a[n][P0] = fast::carry1(a_rho, fast::sel(up, lphi[n][R1], lphi[n][R0]));
+            }
+            const T irho = fast::rcp(fast::fma_(lo.dxl, lo.rho, p.a[P1][0] - a_rho));     // 1 / T_ρ, as fast::project forms it
+            const T m = lo.dxl * lo.rho;
+#pragma unroll
+            for (int n = 0; n < NS; n++)
+                out[n] = fast::settle(m, irho, lphi[n][LO], a[n][P1], a[n][P0], lphi[n][LB], lphi[n][LA]);
+        }
+    }
+
+    template <int PH8>
+    __device__ __forceinline__ void step_remap(const PIPE& p, const T (&pc)[NS][8], T (&out)[NS])
     {
         constexpr int PH = PH8 & 3;
         constexpr int R0 = PH & 3, R1 = (PH - 1) & 3, R2 = (PH - 2) & 3, R3 = (PH - 3) & 3;
@@ -142,7 +225,7 @@ __global__ void __launch_bounds__(64 * kSXRows)
 k_scalar_x(sweep_args a, scalar_planes<NS> ph, int vec)
 {
     constexpr int K = 2, HALO = 4, WIDTH = 64 * K, STRIDE = WIDTH - 2 * HALO;
-    using SW = fused::SpatialSweep<SCHEME, LIM, PROJ, EOS, EXACT, K, real, 0, NS>;
+    using SW = fused::SpatialSweep<SCHEME, LIM, PROJ, EOS, EXACT, K, real, 0, NS, kTransport>;
     using St = fused::Strip<K, real>;
     static_assert(SW::LAG <= HALO, "strip halo");
     const int lane = threadIdx.x;
@@ -238,7 +321,7 @@ k_scalar_y(sweep_args a, scalar_planes<NS> ph)
     }
 
     PIPE pipe(a.dt, a.dx, a.gamma, a.inv_dx, a.dt_dx);
-    ScalarMarch<PIPE, NS> march;
+    ScalarMarch<PIPE, NS, kTransport> march;
     real pc[NS][8];
 #pragma unroll
     for (int n = 0; n < NS; n++)

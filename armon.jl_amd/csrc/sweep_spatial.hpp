@@ -25,6 +25,12 @@
 // under NS > 0 only; the tuned displacement dtu and the fluxes of ρ are there anyway): remapping them inside the state's own
 // loops keeps every plane's q, slope and flux alive next to the state's four, which cost a prototype's fp64 ns = 4 kernels
 // 40-50 VGPRs and two to three waves per SIMD (profiles/scalar_unify_resources.txt).
+//
+// TRANSPORT (NS > 0 only) chooses the planes' rule. kTransportRemap: the one above. kTransportBounded: φ per
+// unit mass — the flux of a plane is the state's own mass flux a0 times the mean of the donor's limited profile of φ over the
+// mass that leaves it, φ* = φ_d ± σ_d·½(1 − ν), σ a plain minmod of φ's two differences, ν = |a0| / m_d, m = Δx_lag·ρ_lag; then
+// φ' = (m φ − ΔA) / dx / ρ', clamped to the smallest and largest of φ at i−1, i, i+1. It shares the mass, the weight ½(1 − ν) of
+// every interface and (exact flavour) the displacement with ρ, and none of the slope ratios or the donor reach.
 #pragma once
 
 #include "lane_shift.hpp"
@@ -36,8 +42,12 @@ namespace fused {
 // One X sweep of the K cells held by each lane. In: pre-sweep (ρ, u, v, E). Out: post-sweep state, valid
 // for the cells at least LAG cells away from both ends of the wave's strip; p/c: EOS of the cells.
 // NS > 0: also the planes phi[0..NS) → o_phi[0..NS), valid for the same cells.
-template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT, int K, typename T = double, int ROW = 0, int NS = 0>
+constexpr int kTransportRemap = 0, kTransportBounded = 1;
+
+template <int SCHEME, int LIM, int PROJ, int EOS, bool EXACT, int K, typename T = double, int ROW = 0, int NS = 0,
+          int TRANSPORT = kTransportRemap>
 struct SpatialSweep {
+    static constexpr bool REMAP = NS > 0 && TRANSPORT == kTransportRemap, BOUNDED = NS > 0 && TRANSPORT == kTransportBounded;
     using TR = PipeTraits<SCHEME, LIM, PROJ, EOS>;
     static constexpr int S = TR::S, W = TR::W, LAG = TR::LAG;
     using S_ = Strip<K, T>;
@@ -127,7 +137,7 @@ struct SpatialSweep {
         }
         // advection flux on the low side of each cell
         S_ a0, a1, a2, a3;    // ρ, ρu, ρv, ρE
-        [[maybe_unused]] S_ k_rm, k_rp, k_disp, k_lf;     // NS > 0: what the planes share with ρ
+        [[maybe_unused]] S_ k_rm, k_rp, k_disp, k_lf;     // NS > 0: what the planes share with ρ (bounded: the displacement only)
         const Sh rL = left_of(l_rho), quL = left_of(q_ua), qvL = left_of(q_ut), qEL = left_of(q_E);
         if (W == 1) {
             const Sh rR = right_of(l_rho), quR = right_of(q_ua), qvR = right_of(q_ut), qER = right_of(q_E);
@@ -141,7 +151,7 @@ struct SpatialSweep {
                 s1.v[k] = phys::slope_minmod(quL[k], q_ua[k], quR[k], r_m, r_p);
                 s2.v[k] = phys::slope_minmod(qvL[k], q_ut[k], qvR[k], r_m, r_p);
                 s3.v[k] = phys::slope_minmod(qEL[k], q_E[k], qER[k], r_m, r_p);
-                if constexpr (NS > 0) {
+                if constexpr (REMAP) {
                     k_rm.v[k] = r_m;
                     k_rp.v[k] = r_p;
                 }
@@ -158,10 +168,8 @@ struct SpatialSweep {
                 a1.v[k] = disp * ((up ? quL[k] : q_ua[k]) - (up ? s1L[k] : s1[k]) * lf);
                 a2.v[k] = disp * ((up ? qvL[k] : q_ut[k]) - (up ? s2L[k] : s2[k]) * lf);
                 a3.v[k] = disp * ((up ? qEL[k] : q_E[k]) - (up ? s3L[k] : s3[k]) * lf);
-                if constexpr (NS > 0) {
-                    k_disp.v[k] = disp;
-                    k_lf.v[k] = lf;
-                }
+                if constexpr (NS > 0) k_disp.v[k] = disp;
+                if constexpr (REMAP) k_lf.v[k] = lf;
             }
         } else {
 #pragma unroll
@@ -191,7 +199,7 @@ struct SpatialSweep {
             o_E.v[k] = d_rho.quo(t_Erho);
         }
         // the planes, one after the other: the t_vrho / o_v lines with φ for ut
-        if constexpr (NS > 0) {
+        if constexpr (REMAP) {
 #pragma unroll
             for (int n = 0; n < NS; n++) {
                 S_ q, a;
@@ -218,6 +226,45 @@ struct SpatialSweep {
                 for (int k = 0; k < K; k++) {
                     const T t_q = d_dx.quo_t(dxl[k] * l_rho[k] * phi[n][k] - (aR[k] - a[k]));
                     o_phi[n].v[k] = Den(o_rho[k]).quo_t(t_q);
+                }
+            }
+        }
+        // the planes per unit mass (§4.17), one after the other: the mass and the weight ½(1 − ν) of every interface once
+        if constexpr (BOUNDED) {
+            S_ m, h;
+#pragma unroll
+            for (int k = 0; k < K; k++) m.v[k] = dxl[k] * l_rho[k];
+            if (W == 1) {
+                const Sh mL = left_of(m);
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const T nu = Den(k_disp[k] > 0 ? mL[k] : m[k]).quo_t(phys::abs_(a0[k]));
+                    h.v[k] = T(0.5) * (1 - nu);
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < NS; n++) {
+                const Sh fL = left_of(phi[n]), fR = right_of(phi[n]);
+                S_ a;
+                if (W == 1) {
+                    S_ s;
+#pragma unroll
+                    for (int k = 0; k < K; k++) s.v[k] = phys::slope_minmod(fL[k], phi[n][k], fR[k], T(1.), T(1.));
+                    const Sh sL = left_of(s);
+#pragma unroll
+                    for (int k = 0; k < K; k++)
+                        a.v[k] = a0[k] * (k_disp[k] > 0 ? fL[k] + sL[k] * h[k] : phi[n][k] - s[k] * h[k]);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; k++) a.v[k] = a0[k] * (k_disp[k] > 0 ? fL[k] : phi[n][k]);
+                }
+                const Sh aR = right_of(a);
+#pragma unroll
+                for (int k = 0; k < K; k++) {
+                    const T t_q = d_dx.quo_t(m[k] * phi[n][k] - (aR[k] - a[k]));
+                    const T lo = phys::mn(phys::mn(fL[k], phi[n][k]), fR[k]), hi = phys::mx(phys::mx(fL[k], phi[n][k]), fR[k]);
+                    const T v = Den(o_rho[k]).quo_t(t_q);
+                    o_phi[n].v[k] = v < lo ? lo : (v > hi ? hi : v);              // (by comparisons: a NaN stays one)
                 }
             }
         }
@@ -265,7 +312,7 @@ struct SpatialSweep {
             q_E.v[k] = n.q_E;
         }
         S_ a0, a1, a2, a3;
-        [[maybe_unused]] S_ k_rm, k_rp, k_lf;     // NS > 0: what the planes share with ρ
+        [[maybe_unused]] S_ k_rm, k_rp, k_lf;     // NS > 0, remap: what the planes share with ρ
         const Sh rL = left_of(l_rho), quL = left_of(q_ua), qvL = left_of(q_ut), qEL = left_of(q_E);
         if (W == 1) {
             const Sh rR = right_of(l_rho), quR = right_of(q_ua), qvR = right_of(q_ut), qER = right_of(q_E);
@@ -285,7 +332,7 @@ struct SpatialSweep {
                 s1.v[k] = fast::slope(r_p, quR[k], q_ua[k], r_m, quL[k]);
                 s2.v[k] = fast::slope(r_p, qvR[k], q_ut[k], r_m, qvL[k]);
                 s3.v[k] = fast::slope(r_p, qER[k], q_E[k], r_m, qEL[k]);
-                if constexpr (NS > 0) {
+                if constexpr (REMAP) {
                     k_rm.v[k] = r_m;
                     k_rp.v[k] = r_p;
                 }
@@ -302,7 +349,7 @@ struct SpatialSweep {
                 a1.v[k] = fast::advect2(disp, lf, -(up ? s1L[k] : s1[k]), up ? quL[k] : q_ua[k]);
                 a2.v[k] = fast::advect2(disp, lf, -(up ? s2L[k] : s2[k]), up ? qvL[k] : q_ut[k]);
                 a3.v[k] = fast::advect2(disp, lf, -(up ? s3L[k] : s3[k]), up ? qEL[k] : q_E[k]);
-                if constexpr (NS > 0) k_lf.v[k] = lf;
+                if constexpr (REMAP) k_lf.v[k] = lf;
             }
         } else {
 #pragma unroll
@@ -323,7 +370,7 @@ struct SpatialSweep {
             fast::project(inv_dx, dxl[k], q, a, aR, o_rho.v[k], o_u.v[k], o_v.v[k], o_E.v[k]);
         }
         // the planes, one after the other: the stages of ρ·ut with q = ρ_lag·φ (fast::lagrange's q_ut) in its slot
-        if constexpr (NS > 0) {
+        if constexpr (REMAP) {
 #pragma unroll
             for (int n = 0; n < NS; n++) {
                 S_ q, a;
@@ -353,6 +400,46 @@ struct SpatialSweep {
                     T t_rho, t_u, t_E;
                     fast::project(inv_dx, dxl[k], qq, al, ah, t_rho, t_u, o_phi[n].v[k], t_E);
                 }
+            }
+        }
+        // the planes per unit mass (§4.17), one after the other: the stages of sweep_stages.hpp's bounded transport
+        if constexpr (BOUNDED) {
+            S_ m, h, irho;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                m.v[k] = dxl[k] * l_rho[k];
+                irho.v[k] = fast::rcp(fast::fma_(dxl[k], l_rho[k], a0[k] - a0R[k]));     // 1 / T_ρ, as fast::project forms it
+            }
+            if (W == 1) {
+                S_ im;
+#pragma unroll
+                for (int k = 0; k < K; k++) im.v[k] = fast::inv_mass(m[k]);
+                const Sh imL = left_of(im);
+#pragma unroll
+                for (int k = 0; k < K; k++) h.v[k] = fast::leaving_weight(a0[k], dtu[k] > 0 ? imL[k] : im[k]);
+            }
+#pragma unroll
+            for (int n = 0; n < NS; n++) {
+                const Sh fL = left_of(phi[n]), fR = right_of(phi[n]);
+                S_ a;
+                if (W == 1) {
+                    S_ s;
+#pragma unroll
+                    for (int k = 0; k < K; k++) s.v[k] = fast::minmod(fR[k] - phi[n][k], phi[n][k] - fL[k]);
+                    const Sh sL = left_of(s);
+#pragma unroll
+                    for (int k = 0; k < K; k++) {
+                        const bool up = dtu[k] > 0;
+                        a.v[k] = fast::carry2(a0[k], h[k], up ? sL[k] : -s[k], up ? fL[k] : phi[n][k]);
+                    }
+                } else {
+#pragma unroll
+                    for (int k = 0; k < K; k++) a.v[k] = fast::carry1(a0[k], dtu[k] > 0 ? fL[k] : phi[n][k]);
+                }
+                const Sh aR = right_of(a);
+#pragma unroll
+                for (int k = 0; k < K; k++)
+                    o_phi[n].v[k] = fast::settle(m[k], irho[k], phi[n][k], a[k], aR[k], fL[k], fR[k]);
             }
         }
     }

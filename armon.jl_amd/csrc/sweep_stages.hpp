@@ -237,6 +237,24 @@ __device__ __forceinline__ void project(Sc inv_dx, T dX, const T (&q)[4], const 
     o_E = T_E * inv;
 }
 
+// ---- bounded transport of a passive scalar φ (per unit mass) -------------------------------------------
+// m = Δx_lag·ρ_lag is the mass of a Lagrangian cell, a the state's mass flux of an interface (advect1 / advect2 of ρ).
+// 1/m to one Newton step: it only feeds ν, the weight of the second-order term
+template <typename T> __device__ __forceinline__ T inv_mass(T m) { return rcp1(m); }
+// ½(1 − ν), ν = |a|/m_d: where in the donor's profile the mean of the mass that leaves it sits, in units of its slope
+template <typename T> __device__ __forceinline__ T leaving_weight(T a, T im_d) { return fma_(T(-0.5), max_(a, -a) * im_d, T(0.5)); }
+// flux of φ: a·φ*, φ* = φ_d + ss·h with ss the donor's limited slope signed towards the interface; first order: a·φ_d
+template <typename T> __device__ __forceinline__ T carry2(T a, T h, T ss, T phi_d) { return a * fma_(ss, h, phi_d); }
+template <typename T> __device__ __forceinline__ T carry1(T a, T phi_d) { return a * phi_d; }
+// φ' = (m φ + A_lo − A_hi) / T_ρ (irho = 1/T_ρ: the 1/dx cancels as in project), kept within φ of the cell and its neighbours
+template <typename T>
+__device__ __forceinline__ T settle(T m, T irho, T phi, T A_lo, T A_hi, T phi_l, T phi_r)
+{
+    const T v = fma_(m, phi, A_lo - A_hi) * irho;
+    const T lo = min_(min_(phi_l, phi), phi_r), hi = max_(max_(phi_l, phi), phi_r);
+    return sel(v < lo, lo, sel(v > hi, hi, v));                // (by comparisons: a NaN stays one)
+}
+
 }  // namespace fast
 
 }  // namespace fused

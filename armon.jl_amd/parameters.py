@@ -102,7 +102,7 @@ class ArmonParameters:
     # ref src/parameters.jl:632-670
     def _init_test(self, test="Sod", domain_size=None, origin=None, cfl=0., maxtime=0.,
                    maxcycle=500_000, gravity=None, scalars=None, viscosity=None, heat_diffusivity=None, diffusion_number=0.5,
-                   diffusion_max_substeps=64, **options):
+                   diffusion_max_substeps=64, scalar_transport=None, **options):
         """``test``: the name of a built-in case, or a ``problem.Problem`` — a user-defined initial state, gamma, EOS and
         boundary types — which is bound here to the run's data type and cell size (``Problem.bind``).
         ``gravity=(gx, gy)``: a uniform body force, applied on the device as a kick at the end of every cycle (DESIGN.md
@@ -117,8 +117,12 @@ class ArmonParameters:
         ``gravity`` does, and a scalar diffuses with its own ``Scalar(..., diffusivity=D)``. ``params.diffusive`` says whether
         anything diffuses. A cycle of step dt applies ``solver.diffusion_substeps(params, dt)`` equal explicit steps:
         ``diffusion_number`` = sigma in (0, 1] bounds dt·2·kappa·(1/dx² + 1/dy²) of one of them (kappa the largest of 4 nu / 3,
-        chi and the D), and more than ``diffusion_max_substeps`` of them in a cycle is an error of the category ``time``."""
-        from .problem import Problem, bind_case
+        chi and the D), and more than ``diffusion_max_substeps`` of them in a cycle is an error of the category ``time``.
+        ``scalar_transport``: ``"remap"`` (the default: φ is remapped as ρ·φ and divided by the new ρ) or
+        ``"bounded"`` (φ is transported per unit mass and stays within the range of its own values); it
+        overrides a problem's own, as ``viscosity`` does. ``"bounded"`` needs at least one scalar. The bound covers the
+        transport: a diffusing scalar diffuses after the sweeps as before."""
+        from .problem import Problem, bind_case, check_scalar_transport
         problem = test if isinstance(test, Problem) else None
         name = str(test)
         if domain_size is None:
@@ -137,6 +141,11 @@ class ArmonParameters:
                                   global_grid=self.N, viscosity=viscosity, heat_diffusivity=heat_diffusivity)
         self.scalars = tuple(self.test.scalars)
         self.scalar_names = tuple(sc.name for sc in self.scalars)
+        if scalar_transport is None:
+            scalar_transport = problem.scalar_transport if problem is not None else "remap"
+        self.scalar_transport = check_scalar_transport(scalar_transport)
+        if self.scalar_transport != "remap" and not self.scalars:
+            solver_error("config", f"scalar_transport = {self.scalar_transport!r} needs at least one passive scalar (scalars=...)")
         self.gravity = self.test.gravity
         self.forced = self.gravity != (0., 0.)
         self.viscosity, self.heat_diffusivity = self.test.viscosity, self.test.heat_diffusivity

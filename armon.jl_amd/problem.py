@@ -88,6 +88,16 @@ def bind_coefficient(value, T, what):
     return r if r != 0 else 0.
 
 
+SCALAR_TRANSPORTS = ("remap", "bounded")     # how the sweeps carry the passive scalars
+
+
+def check_scalar_transport(word):
+    """``word`` if it names a transport rule of the passive scalars; anything else is a configuration error."""
+    if not isinstance(word, str) or word not in SCALAR_TRANSPORTS:
+        solver_error("config", f"scalar_transport must be one of {SCALAR_TRANSPORTS}, got {word!r}")
+    return word
+
+
 def diffusion_description(nu, chi, scalars):
     """What a checkpoint's header and a problem's digest say about a diffusive run: ``{"nu", "chi", "scalars": {name: D}}`` with
     the floats as hex text — or None when nothing diffuses, and the headers and digests of such runs stay what they were."""
@@ -351,13 +361,15 @@ class Problem:
     problem is not held to energy conservation. ``scalars``: a list of ``Scalar`` — passive fields carried by the flow
     (DESIGN.md §4.14); ``from_arrays`` also takes a dict name → ``(NY, NX)`` array. ``viscosity``, ``heat_diffusivity``: the
     constant kinematic shear viscosity and the diffusivity of the specific internal energy, both >= 0; the
-    options of the same names of ``ArmonParameters`` override them. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
+    options of the same names of ``ArmonParameters`` override them. ``scalar_transport``: ``"remap"`` or ``"bounded"``, the rule
+    the sweeps carry the scalars with, overridden likewise. ``domain_size``, ``origin``, ``cfl``, ``maxtime``, ``gravity`` are defaults
     the options of ``ArmonParameters`` override."""
 
     def __init__(self, name, background, regions=(), gamma=7 / 5, eos="perfect_gas", boundaries=Dirichlet, domain_size=(1., 1.),
                  origin=(0., 0.), cfl=0.5, maxtime=0.2, conservative=True, samples=1, gravity=(0., 0.), scalars=(), _deferred=None,
-                 _arrays=None, viscosity=0., heat_diffusivity=0.):
+                 _arrays=None, viscosity=0., heat_diffusivity=0., scalar_transport="remap"):
         self.name = str(name)
+        self.scalar_transport = check_scalar_transport(scalar_transport)
         self.viscosity = bind_coefficient(viscosity, np.float64, "viscosity")
         self.heat_diffusivity = bind_coefficient(heat_diffusivity, np.float64, "heat_diffusivity")
         self.scalars = check_scalars(scalars)

@@ -42,6 +42,7 @@ class SolverStats:   # ref src/solver.jl:13-23
     history: object = None                               # history.History of history_step
     images: list = field(default_factory=list)          # paths of the frames of image_step / image_at_end
     scalars: tuple = ()                                  # names of the run's passive scalars (read with stats.data.scalar(name))
+    scalar_transport: str = "remap"                      # the rule the sweeps carried them with
     diffusion_steps: int = 0                             # launches of armon_hip_diffuse: the sub-steps of every cycle
     mixing: list = field(default_factory=list)          # (cycle, time, {name: mixing.MixingProfile}, {name: mixing.ScalarPDF} or None) of mixing_step / mixing_at_end
 
@@ -897,8 +898,12 @@ def fused_sweep(params, grid, axis, dt, dx, emit_p=False, emit_c=False, emit_dt=
         grid.swap_state()
 
 
+SCALAR_SWEEPS = {"remap": "sweep_scalars", "bounded": "sweep_scalars_bounded"}     # the entry point of a transport rule
+
+
 def scalar_sweep(params, grid, axis, d):
-    """The passive scalars through the sweep ``d`` describes (``armon_hip_sweep_scalars``): enqueued behind
+    """The passive scalars through the sweep ``d`` describes (``armon_hip_sweep_scalars``, DESIGN.md §4.14, or with
+    ``scalar_transport="bounded"`` ``armon_hip_sweep_scalars_bounded``, §4.17 — same arguments, same launch): enqueued behind
     ``armon_hip_sweep(d)``, whose input — the pre-sweep state — is still intact, and before ``swap_state``; then the planes'
     own ping-pong partners take their place. On a periodic axis the planes get their ghosts first, like the state."""
     if params.wrap[int(axis) - 1]:
@@ -907,7 +912,7 @@ def scalar_sweep(params, grid, axis, d):
     phi_in = (C.c_void_p * ns)(*[grid.data[f].ptr for f in grid.scalar_planes])
     phi_out = (C.c_void_p * ns)(*[grid.alt[f].ptr for f in grid.scalar_planes])
     with _k(params, "scalars_x" if axis == Axis.X else "scalars_y"):
-        check(params.fn("sweep_scalars")(params.device.ctx, C.byref(d), ns, phi_in, phi_out))
+        check(params.fn(SCALAR_SWEEPS[params.scalar_transport])(params.device.ctx, C.byref(d), ns, phi_in, phi_out))
     grid.swap_scalars()
 
 
@@ -1605,6 +1610,7 @@ def armon(params):
     stats.images = list(grid.images)
     stats.mixing = list(grid.mixing_samples)
     stats.scalars = tuple(params.scalar_names)
+    stats.scalar_transport = params.scalar_transport
     stats.diffusion_steps = grid.diffusion_steps
     if params.return_data:
         stats.data = grid

@@ -982,6 +982,25 @@ ARMON_API int armon_hip_sweep_scalars(armon_ctx*, const armon_sweep_desc*, int n
                                       double* const* phi_out);
 ARMON_API int armon_hip_sweep_scalars_f32(armon_ctx*, const armon_sweep_desc_f32*, int ns, const float* const* phi_in,
                                           float* const* phi_out);
+/* Bound-preserving transport of the planes: the arguments, the descriptor checks, the refusals, the
+ * launch geometry, the mirrors and what is written are those of armon_hip_sweep_scalars; only the planes' rule differs. φ is
+ * transported per unit mass, with the mass fluxes the state's own remap of ρ computes. Along the sweep axis, per plane:
+ * - Lagrangian mass of cell c: m_c = Δx_lag,c · ρ_lag,c.
+ * - Slope: σ_c = minmod(φ_c − φ_c−1, φ_c+1 − φ_c), not weighted by lengths or masses; projection `euler`: σ = 0.
+ * - Interface on the low side of cell i, mass flux a_i (the advection flux of ρ), donor d = i−1 if it moves up (dt·u* > 0),
+ *   else d = i: ν = |a_i| / m_d, φ*_i = φ_d ± σ_d · ½(1 − ν) (+ when it moves up), A_i = a_i · φ*_i.
+ * - t_q = (m_i φ_i − (A_i+1 − A_i)) / dx, φ'_i = t_q / ρ'_i with ρ' the sweep's own new density.
+ * - φ'_i = min(max(φ'_i, lo_i), hi_i), lo_i / hi_i the smallest / largest of φ_i−1, φ_i, φ_i+1 as the sweep read them (mirrored
+ *   or wrapped ghosts included); taken by comparisons, so a NaN stays a NaN.
+ * Exact flavour: one IEEE operation per operation written, in this order (tests/bounded_restated.py restates it in numpy).
+ * Tuned flavour: the fast:: stages `inv_mass`, `leaving_weight`, `carry1` / `carry2`, `settle` (csrc/sweep_stages.hpp).
+ * Before the clamp φ' is, in real arithmetic, a convex combination of values of the limited profiles of cells i−1, i, i+1
+ * whenever the two outflows of a cell do not exceed its mass; the clamp removes rounding and makes the bound unconditional:
+ * no plane leaves the range of its own values along any line of the sweep axis, ghosts included. */
+ARMON_API int armon_hip_sweep_scalars_bounded(armon_ctx*, const armon_sweep_desc*, int ns, const double* const* phi_in,
+                                              double* const* phi_out);
+ARMON_API int armon_hip_sweep_scalars_bounded_f32(armon_ctx*, const armon_sweep_desc_f32*, int ns, const float* const* phi_in,
+                                                  float* const* phi_out);
 
 /* ---- physical diffusion: viscosity, heat conduction and scalar diffusivity (csrc/diffuse.hip) -------- */
 /* No reference counterpart: the reference solves the inviscid equations. Operator-split, one or more steps per cycle. The rule:
