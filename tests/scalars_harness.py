@@ -54,14 +54,19 @@ def descriptor(blk, axis, scheme, limiter, projection, eos, exact, dt, bc=(1, 1)
     return d
 
 
-def launch(blk, d, inp, out, ns=None, expect=0):
+def launch(blk, d, inp, out, ns=None, expect=0, entry="sweep_scalars"):
     ns = len(inp) if ns is None else ns
     a = (C.c_void_p * max(len(inp), 1))(*[x.ptr if x is not None else None for x in inp])
     b = (C.c_void_p * max(len(out), 1))(*[x.ptr if x is not None else None for x in out])
-    rc = blk.params.fn("sweep_scalars")(blk.dev.ctx, C.byref(d), ns, a, b)
+    rc = blk.params.fn(entry)(blk.dev.ctx, C.byref(d), ns, a, b)
     msg = blk.dev._L.armon_hip_last_error().decode()
     assert (rc == 0) == (expect == 0) and (expect == 0 or rc == expect), (rc, msg)
     return msg
+
+
+def bounded_launch(blk, d, inp, out, ns=None, expect=0):
+    """``launch`` through armon_hip_sweep_scalars_bounded[_f32]."""
+    return launch(blk, d, inp, out, ns, expect, entry="sweep_scalars_bounded")
 
 
 def rand_planes(nx, ny, g, ns, dtype, seed):
@@ -103,9 +108,10 @@ def assert_planes_are(blk, got_in, got, planes, want, axis, what=""):
 
 
 def exact_launch_is_the_restatement(blk, f, planes, want, axis, scheme, limiter, projection, eos, dt, bc=(1, 1), each_alone=True,
-                                    what=""):
+                                    what="", launch=launch):
     """Upload the state ``f`` and ``planes``, run one exact launch of all of them and check it (assert_planes_are,
-    assert_untouched); with ``each_alone``, plane k of the ns-launch is the ns = 1 launch on it. Returns phi_out."""
+    assert_untouched); with ``each_alone``, plane k of the ns-launch is the ns = 1 launch on it. ``launch`` is the entry point's:
+    ``launch`` above, or ``bounded_launch``. Returns phi_out."""
     ns = len(planes)
     P = Planes(blk, ns)
     try:

@@ -3,7 +3,6 @@ restatement (tests/bounded_restated.py), whole runs with ``scalar_transport="bou
 new entry points. The single launches go through the harness of the scalar sweep (tests/scalars_harness.py) with the bounded
 entry point in the place of ``armon_hip_sweep_scalars``; their inputs are those tests/test_bounded_host.py holds the margin of
 the clamp on. Tuned arithmetic prints what it measures (pytest -s)."""
-import ctypes as C
 import functools
 import os
 
@@ -12,7 +11,9 @@ import pytest
 
 import scalars_harness
 from bounded_restated import BCS, CONFIGS, SHAPES, bounded_sweep, launch_inputs, run_cycles
+from bounded_planes import assert_in_local_range
 from scalars_harness import WALLS, Planes, assert_untouched, descriptor, exact_launch_is_the_restatement, rand_planes
+from scalars_harness import bounded_launch as launch
 from sweep_harness import F_HIGH, F_LOW, MARKER, bits, block_cache
 from sweep_reference import STATE, rand_state, real_mask
 
@@ -31,17 +32,6 @@ def blocks():
     yield from block_cache()
 
 
-def launch(blk, d, inp, out, ns=None, expect=0):
-    """scalars_harness.launch through armon_hip_sweep_scalars_bounded[_f32]."""
-    ns = len(inp) if ns is None else ns
-    a = (C.c_void_p * max(len(inp), 1))(*[x.ptr if x is not None else None for x in inp])
-    b = (C.c_void_p * max(len(out), 1))(*[x.ptr if x is not None else None for x in out])
-    rc = blk.params.fn("sweep_scalars_bounded")(blk.dev.ctx, C.byref(d), ns, a, b)
-    msg = blk.dev._L.armon_hip_last_error().decode()
-    assert (rc == 0) == (expect == 0) and (expect == 0 or rc == expect), (rc, msg)
-    return msg
-
-
 ids = lambda v: v if isinstance(v, str) else ("-".join(map(str, v)) if isinstance(v, tuple) else str(v))
 
 
@@ -51,13 +41,12 @@ ids = lambda v: v if isinstance(v, str) else ("-".join(map(str, v)) if isinstanc
 @pytest.mark.parametrize("bc", BCS, ids=lambda v: f"bc{v[0]}{v[1]}")
 @pytest.mark.parametrize("config", CONFIGS, ids=ids)
 @pytest.mark.parametrize("axis,shape,g", SHAPES, ids=ids)
-def test_exact_bounded_sweep_is_the_restatement(blocks, monkeypatch, axis, shape, g, config, bc, dtype):
+def test_exact_bounded_sweep_is_the_restatement(blocks, axis, shape, g, config, bc, dtype):
     """Bit for bit on the real cells, nothing else written, inputs and state untouched; ns = 4, and every plane of it alone."""
-    monkeypatch.setattr(scalars_harness, "launch", launch)
     nx, ny, f, planes, dt, dx = launch_inputs(axis, shape, g, config, dtype)
     want, _, _ = bounded_sweep(f, planes, nx, ny, g, axis, *config, dt, dx, bc[0], bc[1], F_LOW, F_HIGH, dtype)
     blk = blocks(nx, ny, g, dtype)
-    got = exact_launch_is_the_restatement(blk, f, planes, want, axis, *config, dt, bc=bc)
+    got = exact_launch_is_the_restatement(blk, f, planes, want, axis, *config, dt, bc=bc, launch=launch)
     inside = real_mask(nx, ny, g, axis)
     for p, o in zip(planes, got):                          # (the planes hold values in [-1, 2]: the bound is their own range)
         assert o[inside].min() >= p.min() and o[inside].max() <= p.max()
@@ -88,7 +77,8 @@ TUNED = [(0, (250, 9), 4, CONFIGS[0]), (0, (123, 5), 5, CONFIGS[1]), (0, (123, 5
 @pytest.mark.parametrize("axis,shape,g,config", TUNED, ids=ids)
 def test_tuned_bounded_sweep(blocks, axis, shape, g, config, dtype):
     """Within 4 kappa eps of the field maximum from the fp64 restatement of the input the kernel got; exactly the real cells are
-    written; plane k of the ns = 4 launch is the ns = 1 launch, bit for bit; no value leaves its plane's range."""
+    written; plane k of the ns = 4 launch is the ns = 1 launch, bit for bit; no value leaves its plane's range, nor the range
+    of the mirrored input at its own cell and the two beside it."""
     nx, ny, f, planes, dt, dx = launch_inputs(axis, shape, g, config, dtype)
     blk = blocks(nx, ny, g, dtype)
     inside = real_mask(nx, ny, g, axis)
@@ -106,6 +96,7 @@ def test_tuned_bounded_sweep(blocks, axis, shape, g, config, dtype):
             assert np.array_equal(bits(got_in[k]), bits(planes[k])), f"phi_in[{k}] was modified"
             assert ((bits(got[k]) == mark) == ~inside).all(), f"phi_out[{k}]: not exactly the real cells were written"
             assert got[k][inside].min() >= planes[k].min() and got[k][inside].max() <= planes[k].max()
+            assert_in_local_range(got[k], planes[k], inside, nx, ny, g, axis, what=f"plane {k}: ")     # cell by cell: i - 1, i, i + 1
         for k in range(4):
             P.out[0].copy_from_host(blk.marker)
             launch(blk, d, [P.inp[k]], [P.out[0]])
